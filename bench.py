@@ -1,6 +1,14 @@
 """Benchmark: LRS-PnP-DIP outer ADMM iterations/sec (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dip|pnp|dip-pro]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dip|pnp|dip-pro] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets the problem up, runs W untimed and K timed steps and prints the result line.
+--full adds what takes work of its own: `mpsnr` (input, after the steps and, for pnp, the first two
+iterates against the oracle fixture) and `cpu_baseline`.  --dump-outputs DIR writes the solver state
+a caller holds after the last timed step (X, U, L1, L2, Phi) as DIR/<name>.npy (float32; arrays
+above a size cap as a fixed, seeded sample of their elements); the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 
 One "step" = one outer ADMM iteration over a whole synthetic cube, inputs resident in HBM:
 
@@ -32,8 +40,8 @@ Rank 0 prints one JSON line with
                  `peak_split_bf16` / `frac_split_bf16`: the same work against the split-bf16
                  matrix-core ceiling (6 bf16 MFMAs per fp32-accurate product).
                  `roofline.kernels` adds the sparse-coding kernel (k_ista_rs / k_ista_ln2) per launch.
-  cpu_baseline : the oracle timed on this host (rank 0, N = 1): the C ISTA restatement on a bounded
-                 block sample + (dip) the plain-torch DIP restatement (oracle/dip_ref.py) for a few
+  cpu_baseline : (--full) the oracle timed on this host (rank 0, N = 1): the C ISTA restatement on
+                 a bounded block sample + (dip) the plain-torch DIP restatement (oracle/dip_ref.py) for a few
                  steps, both extrapolated to a full outer iteration, + the full ADMM update.
 """
 from __future__ import annotations
@@ -95,7 +103,13 @@ def parse():
                     help="tiled: the 36x36 low_rank_sparsity_mask tiled over the cube (SURVEY.md §8d; the blocks "
                          "share a few observation patterns); random: the same 5.1 %% of missing pixels drawn "
                          "independently (every block its own pattern: the row-split sparse-coding kernel)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: MPSNR before / after the steps "
+                         "(pnp: the first two iterates against the oracle fixture) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the solver state of the last step (X, U, L1, L2, Phi) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group: nccl (= RCCL, one GPU per rank) or gloo (rehearsal: rank r on GPU "
                          "r mod the visible count, so ranks share cuda:0 on a 1-GPU box)")
@@ -173,6 +187,33 @@ class StreamTimer:
 
     def mean_ms(self):
         return float(np.mean([a.elapsed_time(b) for a, b in self.ev])) if self.ev else float("nan")
+
+
+DUMP_FULL_BYTES = 32 << 20      # X is written whole up to this size (configs[1] / [2]: 30 MB)
+DUMP_SAMPLE = 1 << 20           # elements of a sampled array (4 MB each; X above the cap: 4 x as many)
+
+
+def dump_outputs(s, out_dir, rank=0):
+    """--dump-outputs: the state a caller of LrsPnP.step() holds after the last timed step, as
+    <out_dir>/<name>.npy (float32; ranks > 0 append _rank<r>).  X whole up to DUMP_FULL_BYTES; every
+    other array, and a larger X, as the elements at the sorted flat indices
+    default_rng(0).integers(0, numel, count): the same elements in every run (< 52 MB in all)."""
+    import torch
+    if s.X.is_cuda:
+        torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    for name, t in (("X", s.X), ("U", s.U), ("L1", s.L1), ("L2", s.L2), ("Phi", s.phi)):
+        flat = t.detach().reshape(-1)
+        if name != "X" or flat.numel() * 4 > DUMP_FULL_BYTES:
+            count = DUMP_SAMPLE * (4 if name == "X" else 1)
+            if flat.numel() > count:
+                idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), count))
+                flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+            a = flat.cpu().numpy()
+        else:
+            a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a, np.float32))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -421,8 +462,9 @@ def main_dip(args, ctx):
         s = task.s if split else LrsPnP(Y, M, Dct, cfg, image_shape=(H, W))
     finally:
         ops.ista_alpha, ops.ista_pat_prepare = orig_alpha, orig_prep
-    clean_d = torch.from_numpy(clean).cuda()
-    mp0 = mpsnr(s.X, clean_d)
+    if args.full:
+        clean_d = torch.from_numpy(clean).cuda()
+        mp0 = mpsnr(s.X, clean_d)
 
     dip_t, ista_t = StreamTimer(), StreamTimer()
     s.low_rank_dip = dip_t.wrap(s.low_rank_dip, lambda a, k: a[0])
@@ -441,7 +483,8 @@ def main_dip(args, ctx):
     finally:
         ops.ista, ops.ista_pat = orig_ista, orig_ista_pat
     setup_ms = setup_t.mean_ms() * len(setup_t.ev)   # (events complete: timed_steps synchronised)
-    mp1 = mpsnr(s.X, clean_d)
+    if args.dump_outputs:
+        dump_outputs(s, args.dump_outputs, ctx.rank)
     # a time-sliced sparse coding (LrsPnPConfig.ista_slices_dip) is several back-to-back launches:
     # its time per outer iteration is their sum
     n_sl = len(ista_t.ev) / max(1, args.steps)
@@ -519,8 +562,10 @@ def main_dip(args, ctx):
                      "kernels": [ista_entry(ista_name
                                             + (f" over {n_sl:.0f} warm-started launches" if n_sl > 1 else "") + ")",
                                             ista_ms, ista_flops, f"{tag}_ista_hbm_bytes_per_launch", profiled)]},
-        "mpsnr": {"input": mp0, "after_steps": mp1, "outer_iterations_run": args.warmup + args.steps},
     }
+    if args.full:
+        out["mpsnr"] = {"input": mp0, "after_steps": mpsnr(s.X, clean_d),
+                        "outer_iterations_run": args.warmup + args.steps}
     if es:
         out["early_stopping"] = {
             "dip_steps_per_outer_iter": [int(n) for n, _ in timed_runs],
@@ -529,7 +574,7 @@ def main_dip(args, ctx):
             "dip_ms_per_step": dip_ms / n_dip,
             "reference": "main_LRS_PnP_DIP_1-LiP.py on its 36x36x128 data, 1st outer iteration: 28.4 s "
                          "(~165 DIP steps to the stop, 0.127 s per step; BASELINE.md:46)"}
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_dip(s, Y, M, Dct, bb, nit, n_dip, args.cpu_seconds)
     return out
 
@@ -558,7 +603,7 @@ def main_pnp(args, ctx):
         X = D.gather_rows(s.X, ctx)
         return mpsnr(torch.from_numpy(X).cuda(), clean_d) if X is not None else float("nan")
 
-    mp0 = cube_mpsnr()
+    mp0 = cube_mpsnr() if args.full else None
     ista_t = StreamTimer()
     orig_ista = ops.ista
     ops.ista = ista_t.wrap(orig_ista, lambda a, k: k.get("stream") or torch.cuda.current_stream())
@@ -569,14 +614,14 @@ def main_pnp(args, ctx):
         ista_t.on = count[0] >= args.warmup
         count[0] += 1
         s.step()
-        if count[0] <= min(2, args.warmup) and not split:
+        if args.full and count[0] <= min(2, args.warmup) and not split:
             track.append(mpsnr(s.X, clean_d))      # the first two iterates, for the oracle fixture below
 
     elapsed = D.timed_steps(step, args.steps, args.warmup, ctx)
     ops.ista = orig_ista
-    mp1 = cube_mpsnr()
+    if args.dump_outputs:
+        dump_outputs(s, args.dump_outputs, ctx.rank)
     world, rank = ctx.world, ctx.rank
-    mps = [[mp0, mp1]] if split else D.gather_scalars([mp0, mp1], ctx)
     n, K = bb * bb, args.K
     flops = nit * s.nb * 4 * n * K + s.nb * 2 * n * K
     profiled = (H, W, B, bb, nit, K) == (200, 200, 198, 8, 80, 256) and args.mask == "tiled"
@@ -604,15 +649,18 @@ def main_pnp(args, ctx):
                    "parallelism": (f"1 cube in {world} pixel-row slab(s), fp64 Gram all-reduce per iteration"
                                    if split else f"{world} independent cube(s), one per GPU")},
         "roofline": roof, "setup_s": setup_s,
-        "mpsnr": {"input": mp0, "after_steps": mp1, "outer_iterations_run": args.warmup + args.steps,
-                  "per_rank": mps},
     }
+    if args.full:
+        mp1 = cube_mpsnr()
+        mps = [[mp0, mp1]] if split else D.gather_scalars([mp0, mp1], ctx)
+        out["mpsnr"] = {"input": mp0, "after_steps": mp1, "outer_iterations_run": args.warmup + args.steps,
+                        "per_rank": mps}
     fx = os.path.join(REPO, "tests", "golden", "cube200_oracle_2iter.npz")
     if track and (H, W, B, bb, nit, K) == (200, 200, 198, 8, 80, 256) and os.path.exists(fx):
         with np.load(fx, allow_pickle=False) as z:
             out["mpsnr"]["first_two_iterates"] = {"gpu": track[:2], "oracle": [float(v) for v in z["mpsnr"]],
                                                   "oracle_input": float(z["mpsnr_input"])}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_pnp(Y, M, Dct, bb, nit, args.cpu_seconds)
     return out
 

@@ -14,7 +14,8 @@ the seed and the recipe, not the 1.6 M weights:
 drawn in the engine's flat order (tests/dip_ref.param_offsets).  Inputs: data_img5 noisy cube as
 target, lrs_mask as the mask, a seeded U(0,1) input (the reference feeds X + L2/mu2).
 Saved (float32): out after each step (every 5th element), loss per step, per-parameter gradient
-norms of step 0, sigma_max of each conv at step 0.  skip_golden.npz: the same for the skip net of
+norms of step 0, sigma_max of each conv at step 0.  skip_golden.npz: the same (and grad_norms_f64:
+the step-0 gradient norms of the same net run in float64) for the skip net of
 main_LRS_PnP_DIP_pro.py:215-221 (5 scales of 128 channels, 128-channel skips, reflection pad,
 nearest upsample, Sigmoid) with nn.Conv2d-default-scaled weights; its parameters are loaded in
 the reference's parameters() order, which is the engine's flat layout.
@@ -102,9 +103,25 @@ def skip_golden():
         opt.step()
         outs.append(out.detach()[0].numpy().reshape(-1)[::SUB].copy())
         losses.append(float(loss.detach()))
+    # the same step-0 gradient norms with the reference net in float64: the float32 ones above carry
+    # the rounding of whichever convolution algorithm torch picked on the generating host (up to
+    # 2.5e-3 relative here), these do not
+    torch.manual_seed(0)
+    net64 = skip(128, 128, num_channels_down=[128] * 5, num_channels_up=[128] * 5, num_channels_skip=[128] * 5,
+                 filter_size_up=3, filter_size_down=3, upsample_mode="nearest", filter_skip_size=1,
+                 need_sigmoid=True, need_bias=True, pad="reflection", act_fun="LeakyReLU").double()
+    params64 = list(net64.parameters())
+    off = 0
+    with torch.no_grad():
+        for p in params64:
+            p.copy_(torch.from_numpy(flat[off:off + p.numel()]).view_as(p))
+            off += p.numel()
+    mse(T.double() * M.double(), net64(X.double()) * M.double()).backward()
+    gnorm64 = [float(p.grad.norm()) for p in params64]
     np.savez_compressed(os.path.join(HERE, "skip_golden.npz"), seed=np.int64(SEED + 1), steps=np.int64(STEPS),
                         sub=np.int64(SUB), out_sub=np.stack(outs).astype(np.float32),
-                        loss=np.array(losses, np.float64), grad_norms=np.array(gnorm, np.float64))
+                        loss=np.array(losses, np.float64), grad_norms=np.array(gnorm, np.float64),
+                        grad_norms_f64=np.array(gnorm64, np.float64))
     print("skip losses", losses)
 
 

@@ -57,3 +57,36 @@ def test_cpu_baseline_host_fields():
             os.environ.pop("OMP_NUM_THREADS", None)
         else:
             os.environ["OMP_NUM_THREADS"] = saved
+
+
+def test_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """--full is off by default (a plain run measures the headline figure only) and --steps / --warmup
+    are taken as given."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_is_float32_seeded_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: X whole below the cap, the other arrays as the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    g = torch.Generator().manual_seed(0)
+    s = NS(**{k: torch.rand(37, 11, generator=g) for k in ("X", "U", "L1", "L2", "phi")})
+    bench.dump_outputs(s, str(tmp_path / "a"))
+    bench.dump_outputs(s, str(tmp_path / "b"))
+    X = np.load(tmp_path / "a" / "X.npy")
+    assert X.dtype == np.float32 and np.array_equal(X, s.X.numpy())
+    idx = np.sort(np.random.default_rng(0).integers(0, 37 * 11, 100))
+    for name, t in (("U", s.U), ("L1", s.L1), ("L2", s.L2), ("Phi", s.phi)):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b)
+        assert np.array_equal(a, t.numpy().reshape(-1)[idx])
+    monkeypatch.setattr(bench, "DUMP_FULL_BYTES", 64)   # X above the cap: 4 x the sample, seeded too
+    bench.dump_outputs(s, str(tmp_path / "c"))
+    idx4 = np.sort(np.random.default_rng(0).integers(0, 37 * 11, 400))
+    assert np.array_equal(np.load(tmp_path / "c" / "X.npy"), s.X.numpy().reshape(-1)[idx4])

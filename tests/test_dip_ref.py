@@ -27,6 +27,18 @@ def gold(golden):
     return golden("dip_golden.npz")
 
 
+def grads64(nodes, flat, x, target, mask):
+    """Step-0 gradients of the restatement evaluated in float64.  In float32 they depend on the
+    convolution algorithm the host's torch picks for its CPU and thread count: the same code lands
+    1e-5 from the float32 reference's U-Net gradient norms with 2 or 8 threads and 4e-4 with 1 or 4,
+    and the skip net's float32 reference norms themselves sit 2.5e-3 from the float64 ones (loss
+    and output agree to their bounds either way).  So the 1e-4 bound is held in float64, where the
+    host drops out: against the U-Net's recorded norms (5e-6 from the float64 ones) and against
+    the skip net's norms recorded from the reference net run in float64 (grad_norms_f64)."""
+    tr = dip_ref.RefTrainer(nodes, flat.double(), lr=0.1)
+    return tr.step(x.double(), target.double(), mask.double())[2]
+
+
 def test_restatement_matches_reference_unet(gold):
     torch.manual_seed(0)
     units = lipschitz_unet_units(128, 128, 128)
@@ -36,6 +48,7 @@ def test_restatement_matches_reference_unet(gold):
     offs, _ = dip_ref.param_offsets(units, 128)
     sig = [float(dip_ref.sigma_scale(dip_ref.views(flat, units, i, offs)[0])[0]) for i in range(len(units))]
     np.testing.assert_allclose(sig, gold["sigma"], rtol=2e-6)
+    flat0 = flat.clone()
     tr = dip_ref.RefTrainer(units, flat, lr=0.1)
     sub = int(gold["sub"])
     for it in range(int(gold["steps"])):
@@ -51,8 +64,9 @@ def test_restatement_matches_reference_unet(gold):
         assert rel(out.numpy().reshape(-1)[::sub], gold["out_sub"][0]) < 1e-5
         if it == 0:
             gn = []
+            g64 = grads64(units, flat0, x, target, mask)
             for i in range(len(units)):
-                W, b, gm, be = dip_ref.views(g, units, i, offs)
+                W, b, gm, be = dip_ref.views(g64, units, i, offs)
                 gn += [float(W.norm()), float(b.norm()), float(gm.norm()) if gm is not None else 0.0,
                        float(be.norm()) if be is not None else 0.0]
             gn, ref = np.array(gn), gold["grad_norms"]
@@ -66,6 +80,7 @@ def test_restatement_matches_reference_skip(golden):
     nodes = skip_nodes(128, 128)
     flat = torch.from_numpy(flat_params(nodes, int(gold["seed"])))
     x, target, mask = (torch.from_numpy(a) for a in problem(int(gold["seed"])))
+    g64 = grads64(nodes, flat, x, target, mask)
     tr = dip_ref.RefTrainer(nodes, flat, lr=0.1)
     sub = int(gold["sub"])
     out, loss, g = tr.step(x, target, mask)
@@ -75,11 +90,11 @@ def test_restatement_matches_reference_skip(golden):
     offs, _ = dip_ref.param_offsets(nodes, 128)
     gn = []
     for i in range(len(nodes)):
-        for v in dip_ref.views(g, nodes, i, offs):
+        for v in dip_ref.views(g64, nodes, i, offs):
             if v is not None:
                 gn.append(float(v.norm()))
-    gn, ref = np.array(gn), gold["grad_norms"]
-    assert gn.shape == ref.shape
+    gn, ref = np.array(gn), gold["grad_norms_f64"]
+    assert gn.shape == ref.shape == gold["grad_norms"].shape
     big = ref > 1e-4 * ref.max()
     np.testing.assert_allclose(gn[big], ref[big], rtol=1e-4)
 

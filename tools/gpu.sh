@@ -57,7 +57,7 @@ bench)
     timeout -k 10 $t python bench.py "$@" > $O/$n.json 2> $O/$n.err || { tail $O/$n.err; exit 1; }
     python -c "import json; d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]); print('$n', d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('frac'), (d.get('cpu_baseline') or {}).get('value'))"
   }
-  line default 300
+  line default 300 --full
   line random_mask 300 --mask random --no-cpu-baseline
   line dip_pro 400 --workload dip-pro --steps 3 --warmup 1 --no-cpu-baseline
   line dip_pro_200 300 --workload dip-pro --cube 200x200x198 --steps 3 --warmup 1 --no-cpu-baseline
@@ -99,7 +99,7 @@ profile)
   for wl in ${WORKLOADS:-dip pnp}; do
     if [ $wl = pnp ]; then S="--steps 10 --warmup 2"; else S="--steps 3 --warmup 1"; fi
     B="bench.py --workload $wl $S --no-cpu-baseline"
-    timeout -k 10 400 python bench.py --workload $wl $S > $P/${wl}_bench.json 2> $P/${wl}_bench.err || { tail $P/${wl}_bench.err; exit 1; }
+    timeout -k 10 400 python bench.py --workload $wl $S --full > $P/${wl}_bench.json 2> $P/${wl}_bench.err || { tail $P/${wl}_bench.err; exit 1; }
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $P/${wl}_trace -o run --output-format csv -- python3 $B > $P/${wl}_trace.log 2>&1 || { tail $P/${wl}_trace.log; exit 1; }
     timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE -d $P/${wl}_fetch -o run --output-format csv -- python3 $B > $P/${wl}_fetch.log 2>&1 || { tail $P/${wl}_fetch.log; exit 1; }
     timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE -d $P/${wl}_write -o run --output-format csv -- python3 $B > $P/${wl}_write.log 2>&1 || { tail $P/${wl}_write.log; exit 1; }
