@@ -160,6 +160,35 @@ int lrs_ista_pat_f32(const float *Yb, const uint8_t *obs_pat, int64_t npat, cons
                      int64_t ntiles, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
                      const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi,
                      const lrs_ista_opts *opts, void *ws, size_t ws_bytes, void *stream);
+/* ---- Dictionary learning: the dictionary step of masked alternating minimisation -------------
+ * The reference loads its dictionary from trained_dictionary.mat (main_LRS_PnP.py:159-160, variable
+ * Dictionary), whose training code was never published.  These calls learn it from the observed
+ * blocks: with the coefficients A = coefs fixed (a sparse-coding pass of lrs_ista_f32 /
+ * lrs_ista_pat_f32 with LRS_PROX_SOFT), n_inner majorisation-minimisation iterations (Yaghoobi,
+ * Blumensath, Davies) of
+ *   min_D  sum_j 1/2 ||obs_j .* (y_j - D a_j)||^2   subject to ||d_k||_2 <= 1:
+ *   R = obs .* (Yb - coefs D^T);  obj = 1/2 ||R||_F^2;  G = R^T coefs;
+ *   u_k = d_k + g_k / c;  d_k = u_k / max(1, ||u_k||_2)
+ * with c >= lambda_max(coefs^T coefs), so obj cannot rise.  Layouts are the ISTA calls': Yb, obs
+ * [nb][n_pad] (columns >= n never contribute), coefs [nb][K], D n x K row-major.  The three products
+ * run on the bf16 matrix cores (three-term split, fp32-GEMM accuracy); obj and the column norms are
+ * fp64; every sum runs in a fixed order (bit-identical reruns).  K <= 512, nb <= 2^24
+ * (LRS_E_UNSUPPORTED above), n_pad % 16 == 0.
+ *   lrs_dict_workspace: bytes of `ws` for both calls below at these sizes (0: bad sizes).
+ *   lrs_dict_stats_f32: H = coefs^T coefs (K x K float32) and *c = max_k sum_l |H_kl| (device
+ *     double, fp64 sums over the stored H: Gershgorin's bound on lambda_max).
+ *   lrs_dict_update_f32: n_inner iterations in place on D.  c: device double (read on the device;
+ *     c = 0, every coefficient zero, leaves D as it is); an atom no block uses (H_kk = 0) gets
+ *     g_k = 0.  obj: n_inner + 1 device doubles, the objective before each iteration and after the last.
+ *   lrs_dict_normalise_f32: every column of D with a non-zero norm scaled to unit norm
+ *     (columnNormalise.m), the last step of a training run. */
+size_t lrs_dict_workspace(int64_t n, int64_t n_pad, int64_t K, int64_t nb);
+int lrs_dict_stats_f32(const float *coefs, int64_t nb, int64_t K, float *H, double *c, void *ws,
+                       size_t ws_bytes, void *stream);
+int lrs_dict_update_f32(const float *Yb, const uint8_t *obs, const float *coefs, float *D, int64_t n,
+                        int64_t n_pad, int64_t K, int64_t nb, const double *c, int n_inner, double *obj,
+                        void *ws, size_t ws_bytes, void *stream);
+int lrs_dict_normalise_f32(float *D, int64_t n, int64_t K, void *stream);
 /* NLmeansfilter(g, 3, 3, h) (LRS-PnP(Matlab Code)/NLmeansfilter.m:18-78, the prox of
  * pnp_ista.m:30) of nvec columns of length K, fp64, 'symmetric' padding. */
 int lrs_nlm_matlab_col_f32(const float *g, int64_t ldg, float *out, int64_t ldo, int64_t K,

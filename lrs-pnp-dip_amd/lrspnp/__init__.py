@@ -6,5 +6,6 @@ reference's own function names for drop-in use.
 """
 from ._lib import LrsError, build, lib  # noqa: F401
 from .solver import LrsPnP, LrsPnPConfig  # noqa: F401
+from .dictlearn import DictLearnConfig, learn_dictionary  # noqa: F401
 
-__version__ = "0.1.0"
+__version__ = "0.2.0"

@@ -90,7 +90,11 @@ def _declare(L):
         "lrs_ista_pat_prepare": (i32, [vp, i64, i64, vp, i64, i64, vp, sz, vp]),
         "lrs_ista_pat_f32": (i32, [vp, vp, i64, vp, i64, i64, i64, i64, i64, vp, vp, i32, i32, vp, vp,
                                    c.POINTER(IstaOpts), vp, sz, vp]),
-        "lrs_ssim_f32": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "lrs_dict_workspace": (sz, [i64, i64, i64, i64]),
+        "lrs_dict_stats_f32": (i32, [vp, i64, i64, vp, vp, vp, sz, vp]),
+        "lrs_dict_update_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp, i32, vp, vp, sz, vp]),
+        "lrs_dict_normalise_f32": (i32, [vp, i64, i64, vp]),
+        "lrs_ssim_f32":(i32, [vp, vp, i32, i32, i32, vp, vp]),
         "lrs_psnr_workspace": (sz, [i64, i64]),
         "lrs_psnr_bands_f32": (i32, [vp, vp, i64, i64, vp, vp, sz, vp]),
         "lrs_svt_workspace": (sz, [i64, i64]),

@@ -78,6 +78,39 @@ def load_mat(path: str) -> dict:
                        "tools/convert_mat73.py under a Python that has h5py and keep the .npz beside it")
 
 
+def save_mat5(path: str, variables: dict) -> str:
+    """Write real float32 / float64 arrays (up to 2-D here is all the project needs; any rank is
+    accepted) as an uncompressed MAT v5 file that ``scipy.io.loadmat`` and MATLAB read -- the format
+    of the reference's ``trained_dictionary.mat`` (main_LRS_PnP.py:159-160).  Other dtypes are
+    converted to float64."""
+    import struct
+
+    def element(mi_type: int, payload: bytes) -> bytes:
+        pad = (-len(payload)) % 8
+        return struct.pack("<II", mi_type, len(payload)) + payload + b"\0" * pad
+
+    out = [("MATLAB 5.0 MAT-file, written by lrspnp.matio.save_mat5".ljust(116).encode("ascii") + b"\0" * 8
+            + struct.pack("<H", 0x0100) + b"IM")]
+    for name, value in variables.items():
+        a = np.asarray(value)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.ndim < 2:
+            a = a.reshape(1, -1)
+        mx_class, mi_type = (7, 7) if a.dtype == np.float32 else (6, 9)   # mxSINGLE/miSINGLE, mxDOUBLE/miDOUBLE
+        nm = name.encode("ascii")
+        if not nm or len(nm) > 63:
+            raise ValueError(f"MAT v5 variable name {name!r}: 1..63 ASCII characters")
+        body = (element(6, struct.pack("<II", mx_class, 0))                          # array flags (miUINT32)
+                + element(5, struct.pack(f"<{a.ndim}i", *a.shape))                   # dimensions (miINT32)
+                + element(1, nm)                                                     # name (miINT8)
+                + element(mi_type, np.asfortranarray(a).astype(a.dtype.newbyteorder("<")).tobytes(order="F")))
+        out.append(struct.pack("<II", 14, len(body)) + body)                         # miMATRIX
+    with open(path, "wb") as f:
+        f.write(b"".join(out))
+    return path
+
+
 def cube_from_h5(arr: np.ndarray) -> np.ndarray:
     """h5py-orientation cube (H', W', B, 1) -> (B, H, W) float32: the reference's
     ``.transpose((-1, 2, 1, 0))`` (main_LRS_PnP.py:174) without the leading batch axis."""

@@ -15,7 +15,7 @@ from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLA
                    device_lib, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -235,6 +235,68 @@ def ista_pat(Yb, obs_pat, plan, ntiles: int, K: int, n: int, alpha, thr, Nit: in
                              _p(thr), int(Nit), int(prox), _p(coefs) if want_coefs else None, _p(phi), opts, _p(ws),
                              ws.numel(), _s(stream)), "lrs_ista_pat_f32")
     return (phi, coefs) if want_coefs else phi
+
+
+def dict_workspace(n: int, n_pad: int, K: int, nb: int, device) -> torch.Tensor:
+    """Device workspace of dict_stats() / dict_update() at these sizes (lrs_dict_workspace)."""
+    nbytes = int(lib().lrs_dict_workspace(int(n), int(n_pad), int(K), int(nb)))
+    if nbytes == 0:
+        raise LrsError(f"lrs_dict_workspace: sizes not served (n {n}, n_pad {n_pad}, K {K}, nb {nb}; K <= 512)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def dict_stats(coefs, H=None, c=None, ws=None, stream=None):
+    """H = coefs^T coefs (K, K) float32 and c = max_k sum_l |H_kl| (a float64 device tensor of one
+    element: Gershgorin's bound on lambda_max(H), the dictionary step's 1 / step size)."""
+    L = device_lib()
+    _dev(coefs, torch.float32, "coefs")
+    nb, K = coefs.shape
+    if H is None:
+        H = torch.empty((K, K), dtype=torch.float32, device=coefs.device)
+    if c is None:
+        c = torch.empty(1, dtype=torch.float64, device=coefs.device)
+    _dev(H, torch.float32, "H")
+    _dev(c, torch.float64, "c")
+    if ws is None:
+        ws = dict_workspace(16, 16, K, nb, coefs.device)
+    check(L.lrs_dict_stats_f32(_p(coefs), nb, K, _p(H), _p(c), _p(ws), ws.numel(), _s(stream)), "lrs_dict_stats_f32")
+    return H, c
+
+
+def dict_update(Yb, obs, coefs, D, n: int, c, n_inner: int, obj=None, ws=None, stream=None):
+    """n_inner majorisation-minimisation iterations of the masked dictionary step, in place on D
+    (n, K): u_k = d_k + (R^T coefs)_k / c, d_k = u_k / max(1, ||u_k||), R = obs .* (Yb - coefs D^T).
+    c: dict_stats()'s device scalar.  Returns obj (n_inner + 1,) float64 on the device: 1/2 ||R||^2
+    before each iteration and after the last."""
+    L = device_lib()
+    _dev(Yb, torch.float32, "Yb")
+    _dev(obs, torch.uint8, "obs")
+    _dev(coefs, torch.float32, "coefs")
+    _dev(D, torch.float32, "D")
+    _dev(c, torch.float64, "c")
+    nb, n_pad = Yb.shape
+    K = D.shape[1]
+    if D.shape[0] != n or coefs.shape != (nb, K) or obs.shape != Yb.shape:
+        raise LrsError(f"dict_update: D {tuple(D.shape)}, coefs {tuple(coefs.shape)}, obs {tuple(obs.shape)} do not "
+                       f"match Yb {tuple(Yb.shape)} with n = {n}")
+    if obj is None:
+        obj = torch.empty(int(n_inner) + 1, dtype=torch.float64, device=Yb.device)
+    _dev(obj, torch.float64, "obj")
+    if obj.numel() < int(n_inner) + 1:
+        raise LrsError("dict_update: obj holds fewer than n_inner + 1 values")
+    if ws is None:
+        ws = dict_workspace(n, n_pad, K, nb, Yb.device)
+    check(L.lrs_dict_update_f32(_p(Yb), _p(obs), _p(coefs), _p(D), n, n_pad, K, nb, _p(c), int(n_inner), _p(obj),
+                                _p(ws), ws.numel(), _s(stream)), "lrs_dict_update_f32")
+    return obj
+
+
+def dict_normalise(D, stream=None):
+    """Every column of D (n, K) with a non-zero norm scaled to unit norm, in place (columnNormalise.m)."""
+    L = device_lib()
+    _dev(D, torch.float32, "D")
+    check(L.lrs_dict_normalise_f32(_p(D), D.shape[0], D.shape[1], _s(stream)), "lrs_dict_normalise_f32")
+    return D
 
 
 def nlm_matlab_col(g: torch.Tensor, h, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:

@@ -71,6 +71,9 @@ class LrsPnPConfig:
     # pattern, 2 K^2 instead of 4 n K FLOP per block and iteration): "auto" when the library's cost
     # model prefers it (few patterns, n > K / 2), "on" whenever the block length allows it, "off".
     ista_patterns: str = "auto"
+    # D="learn": the lrspnp.dictlearn.DictLearnConfig of the training run (None: its defaults); bb and
+    # lambda_ista are always this config's own
+    dict_cfg: object = None
 
     @staticmethod
     def dip_1lip(**kw) -> "LrsPnPConfig":
@@ -118,7 +121,17 @@ class LrsPnP:
         dev = torch.device(device)
         f = lambda a: torch.as_tensor(np.asarray(a, np.float32) if not isinstance(a, torch.Tensor) else a,
                                       dtype=torch.float32).to(dev).contiguous()
-        self.Y, self.M, self.D = f(Y), f(M), f(D)
+        self.Y, self.M = f(Y), f(M)
+        self.dict_history = None
+        if isinstance(D, str):
+            # the dictionary learned from this solver's own observation (lrspnp.dictlearn)
+            if D != "learn":
+                raise LrsError(f"D must be an n x K array or 'learn', got {D!r}")
+            from dataclasses import replace
+            from .dictlearn import DictLearnConfig, learn_dictionary
+            dcfg = replace(cfg.dict_cfg or DictLearnConfig(), bb=cfg.bb, lambda_ista=cfg.lambda_ista)
+            D, self.dict_history = learn_dictionary(self.Y, self.M, dcfg, device=dev)
+        self.D = f(D)
         self.P, self.B = self.Y.shape
         n, self.K = self.D.shape
         if n != cfg.bb * cfg.bb:
