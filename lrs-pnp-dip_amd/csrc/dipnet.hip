@@ -17,6 +17,7 @@
 #include "dip_gemm.h"
 #include "dip_sm.h"
 #include "dip_dir.h"
+#include "ista_paths.h"
 
 using namespace lrs;
 
@@ -927,7 +928,8 @@ __global__ void k_image_to_unfolded(const float *__restrict__ img, int64_t H, in
 
 }  // namespace
 
-// Dense fp32-accurate GEMM for the library's other components (the K > 512 ISTA path, ista.hip):
+// Dense fp32-accurate GEMM for the library's other components (the K > 512 ISTA path,
+// ista_generic.hip; declared in ista_paths.h):
 // C[M][N] = op(A) op(B) with the DIP engine's split-bf16 / f32 kernels, split-K summed in fixed
 // order (deterministic).  part: >= dense_gemm_part_floats(M, N, K) floats.
 namespace lrs {

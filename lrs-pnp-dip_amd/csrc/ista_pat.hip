@@ -27,16 +27,12 @@
 #include <algorithm>
 #include <vector>
 
+#include "ista_paths.h"
 #include "ista_prox.h"
 
 namespace lrs {
 
-// row-split kernel's dictionary images (ista_rs.hip)
-int ista_rs_images(const float *D, int64_t n, int64_t K, int NT, int NQ, float4 *DAf, float4 *DTf, hipStream_t st);
-
 typedef double pg_d4 __attribute__((ext_vector_type(4)));
-
-static int pat_nq(int64_t K) { return K <= 64 ? 4 : K <= 128 ? 8 : K <= 256 ? 16 : 32; }
 
 // ---- Q_p = D^T diag(m_p) D ----------------------------------------------------------------------
 // grid (upper 64 x 64 block pairs (bi <= bj) of the KP x KP Gram, npat), 256 threads: wave w forms
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
 
 // n_pad: the images' row count (the kernels index them with NT = n_pad / 16)
 static int64_t pat_images_floats(int64_t n_pad, int64_t K, int64_t npat) {
-    const int64_t NT = round_up(n_pad, 16) / 16, NQ = pat_nq(K);
+    const int64_t NT = round_up(n_pad, 16) / 16, NQ = ista_nq(K);
     return 2 * NT * NQ * 64 * 4 + npat * NQ * NQ * 256;
 }
 
@@ -366,7 +362,7 @@ int ista_pat_prepare(const float *D, int64_t n, int64_t K, const uint8_t *obs_pa
     // sized from n_pad, which sets the images' row count (lrs_ista_pat_workspace(n) covers the
     // n_pad = round_up(n, 16) every caller of the solver uses; a larger n_pad needs its own size)
     if (!ws || ws_bytes < (size_t)pat_images_floats(n_pad, K, npat) * sizeof(float)) return LRS_E_WORKSPACE;
-    const int NQ = pat_nq(K);
+    const int NQ = ista_nq(K);
     const int NT = (int)(n_pad / 16);
     if ((int64_t)NT * NQ * 1024 >= ((int64_t)1 << 31)) return LRS_E_UNSUPPORTED;   // 32-bit buffer offsets
     if (n > INT32_MAX / 2 || npat > 65535) return LRS_E_UNSUPPORTED;
@@ -388,7 +384,7 @@ int ista_pat_launch(const float *Yb, const uint8_t *obs_pat, int64_t npat, const
                     const float *x0) {
     if (K < 1 || K > 512) return LRS_E_UNSUPPORTED;
     if (!ws || ws_bytes < (size_t)pat_images_floats(n_pad, K, npat) * sizeof(float)) return LRS_E_WORKSPACE;
-    const int NQ = pat_nq(K);
+    const int NQ = ista_nq(K);
     const int NT = (int)(n_pad / 16);
     if ((int64_t)NT * NQ * 1024 >= ((int64_t)1 << 31)) return LRS_E_UNSUPPORTED;
     if (n > INT32_MAX / 2 || npat > 65535) return LRS_E_UNSUPPORTED;
@@ -474,17 +470,11 @@ extern "C" int lrs_ista_pat_f32(const float *Yb, const uint8_t *obs_pat, int64_t
                                 int64_t n, int64_t n_pad, int64_t K, int64_t nb, const float *alpha, const double *thr,
                                 int Nit, int prox, float *coefs, float *phi, const lrs_ista_opts *opts, void *ws,
                                 size_t ws_bytes, void *stream) {
-    if (!Yb || !obs_pat || !plan || !alpha || !thr || !phi || n <= 0 || nb < 0 || Nit < 0 || K <= 0 || npat < 1 ||
-        ntiles < 0)
-        return LRS_E_INVALID;
-    if (n_pad % 16 != 0 || n_pad < n || n_pad > (int64_t)1 << 20 || nb > INT32_MAX) return LRS_E_INVALID;
-    if (prox != LRS_PROX_NLM && prox != LRS_PROX_SOFT && prox != LRS_PROX_NLM_MATLAB) return LRS_E_INVALID;
-    if (ntiles > (nb + 15) / 16 + npat) return LRS_E_INVALID;
-    const int64_t max_wg = opts ? opts->max_workgroups : 0;
-    if (max_wg < 0) return LRS_E_INVALID;
-    if (opts && opts->precision != LRS_ISTA_F32 && opts->precision != LRS_ISTA_SPLIT_BF16) return LRS_E_INVALID;
+    if (!Yb || !obs_pat || !plan || !alpha || !thr || !phi || npat < 1 || ntiles < 0) return LRS_E_INVALID;
+    if (const int rc = lrs::ista_check_args(n, n_pad, K, nb, Nit, prox, opts)) return rc;
+    if (nb > INT32_MAX || ntiles > (nb + 15) / 16 + npat) return LRS_E_INVALID;
     if (opts && opts->algorithm != LRS_ISTA_ALGO_AUTO) return LRS_E_INVALID;
-    if (opts && opts->warm_start != 0 && opts->warm_start != 1) return LRS_E_INVALID;
+    const int64_t max_wg = opts ? opts->max_workgroups : 0;
     const bool warm = opts && opts->warm_start;
     if (warm && !coefs) return LRS_E_UNSUPPORTED;
     if (K > 512) return LRS_E_UNSUPPORTED;

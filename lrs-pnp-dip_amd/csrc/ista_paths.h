@@ -1,0 +1,48 @@
+// The sparse-coding paths behind lrs_ista_f32 / lrs_ista_pat_f32: the one declaration of every
+// function the ISTA translation units call across files, and the host helpers they share.  Every
+// definer includes this header, so a signature that drifts fails to compile instead of linking.
+#pragma once
+#include "lrs_common.h"
+
+namespace lrs {
+
+// 16-atom tiles the row-split and per-pattern kernels are instantiated for (K <= 512)
+inline int ista_nq(int64_t K) { return K <= 64 ? 4 : K <= 128 ? 8 : K <= 256 ? 16 : 32; }
+
+// The argument checks lrs_ista_f32 and lrs_ista_pat_f32 share.  Each entry adds its own: the
+// pointers, the bound on nb, and the lrs_ista_opts.algorithm values it accepts.
+inline int ista_check_args(int64_t n, int64_t n_pad, int64_t K, int64_t nb, int Nit, int prox,
+                           const lrs_ista_opts *opts) {
+    if (n <= 0 || nb < 0 || Nit < 0 || K <= 0) return LRS_E_INVALID;
+    if (n_pad % 16 != 0 || n_pad < n || n_pad > (int64_t)1 << 20) return LRS_E_INVALID;
+    if (prox != LRS_PROX_NLM && prox != LRS_PROX_SOFT && prox != LRS_PROX_NLM_MATLAB) return LRS_E_INVALID;
+    if (!opts) return LRS_OK;
+    if (opts->precision != LRS_ISTA_F32 && opts->precision != LRS_ISTA_SPLIT_BF16) return LRS_E_INVALID;
+    if (opts->max_workgroups < 0) return LRS_E_INVALID;
+    if (opts->warm_start != 0 && opts->warm_start != 1) return LRS_E_INVALID;
+    return LRS_OK;
+}
+
+// ---- ista_rs.hip: the row-split kernel (any n, K <= 512, every prox) ---------------------------
+size_t ista_rs_workspace(int64_t n, int64_t K);
+// the two fragment-ordered dictionary images (also read by the per-pattern Gram kernel)
+int ista_rs_images(const float *D, int64_t n, int64_t K, int NT, int NQ, float4 *DAf, float4 *DTf, hipStream_t st);
+int ista_rs_launch(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
+                   const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
+                   size_t ws_bytes, int64_t max_wg, hipStream_t st, const float *x0);
+// NLmeansfilter(g, 3, 3, h) of nvec columns of length K (the MATLAB-variant prox)
+int nlm_matlab_col_launch(const float *g, int64_t ldg, float *out, int64_t ldo, int64_t K, int64_t nvec, double h,
+                          const double *h_per_vec, hipStream_t st);
+
+// ---- ista_generic.hip: the dense-GEMM path (any K; the only one for K > 512) -------------------
+size_t ista_generic_workspace(int64_t n, int64_t K);
+int ista_generic(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
+                 const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
+                 size_t ws_bytes, hipStream_t st);
+
+// ---- dipnet.hip: C = op(A) op(B), fp32-accurate, split-K partials in `part` --------------------
+int64_t dense_gemm_part_floats(int M, int N, int K);
+int dense_gemm(int TA, int TB, const float *A, const float *B, float *C, int M, int N, int K, float *part,
+               int64_t part_cap, hipStream_t st);
+
+}  // namespace lrs

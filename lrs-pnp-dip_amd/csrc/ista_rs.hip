@@ -31,10 +31,10 @@
 
 #include <algorithm>
 
+#include "ista_paths.h"
 #include "ista_prox.h"
 
 namespace lrs {
-
 
 struct IstaRsParams {
     const float *Yb;       // [nb][n_pad]
@@ -361,11 +361,9 @@ static int cu_count() {
     return g_cu_count;
 }
 
-static int rs_nq(int64_t K) { return K <= 64 ? 4 : K <= 128 ? 8 : K <= 256 ? 16 : 32; }
-
 size_t ista_rs_workspace(int64_t n, int64_t K) {
     const int64_t n_pad = round_up(n, 16);
-    return (size_t)2 * n_pad * rs_nq(K) * 16 * sizeof(float);
+    return (size_t)2 * n_pad * ista_nq(K) * 16 * sizeof(float);
 }
 
 // Waves per workgroup S: the per-SIMD makespan ceil(tiles S / SIMDs) / S, smallest S on ties;
@@ -427,7 +425,7 @@ int ista_rs_launch(const float *Yb, const uint8_t *obs, const float *D, int64_t 
                    const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
                    size_t ws_bytes, int64_t max_wg, hipStream_t st, const float *x0) {
     if (K < 1 || K > 512) return LRS_E_UNSUPPORTED;
-    const int NQ = rs_nq(K);
+    const int NQ = ista_nq(K);
     const int NT = (int)(n_pad / 16);
     // the dictionary images are addressed by 32-bit buffer offsets (t * NQ + k) * 1024
     if ((int64_t)NT * NQ * 1024 >= ((int64_t)1 << 31)) return LRS_E_UNSUPPORTED;
@@ -436,12 +434,7 @@ int ista_rs_launch(const float *Yb, const uint8_t *obs, const float *D, int64_t 
     if (!ws || ws_bytes < ista_rs_workspace(n_pad, K)) return LRS_E_WORKSPACE;
     float4 *DAf = reinterpret_cast<float4 *>(ws);
     float4 *DTf = DAf + (size_t)NT * NQ * 64;
-    {
-        const int64_t total = (int64_t)NT * NQ * 64;
-        const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(k_ista_rs_prep, dim3(blocks), dim3(256), 0, st, D, (int)n, (int)K, NT, NQ, DAf, DTf);
-        LRS_CHECK_LAUNCH();
-    }
+    if (const int rc = ista_rs_images(D, n, K, NT, NQ, DAf, DTf, st)) return rc;
     IstaRsParams p{Yb, obs, DAf, DTf, alpha, thr, coefs, phi, (int)n_pad, (int)K, Nit, prox, nb, 7.0, x0};
     switch (NQ) {
     case 4: return launch_rs<4, 2>(p, NT, max_wg, st);

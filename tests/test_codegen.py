@@ -1,7 +1,7 @@
 """Register allocation of the configs[1] sparse-coding kernel, read from the built library (CPU).
 
 k_ista_ln2 (the bb = 8 kernel, main_LRS_PnP.py:131-149) fills all 512 registers of its SIMD.  LLVM
-gives the product instantiation <256, false, 1, true, 1> round 1's allocation (30-32 AGPRs, no
+gives the product instantiation <256, 1> round 1's allocation (30-32 AGPRs, no
 spills) only while ista.hip also instantiates <..., 0> (compiled alone the same source
 keeps fewer allocas to the backend, ends at 82 AGPRs with 241 v_accvgpr moves, and configs[1] loses
 2.8 %).  No source attribute controls it (amdgpu_waves_per_eu, amdgpu_num_vgpr and
@@ -22,7 +22,7 @@ from lrspnp import _lib
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-PRODUCT = "_ZN3lrs10k_ista_ln2ILi256ELb0ELi1ELb1ELi1EEEvNS_10IstaParamsE"
+PRODUCT = "_ZN3lrs10k_ista_ln2ILi256ELi1EEEvNS_10IstaParamsE"
 
 
 def code_objects(so):

@@ -535,6 +535,34 @@ def test_ista_both_product_precisions_match_oracle():
     assert np.array_equal(out[None][0], out[1][0])      # no process-wide mode: the default is per call
 
 
+def test_ista_soft_both_product_precisions_match_oracle():
+    """The resident kernels with the soft prox: k_ista_res<256, true> (exact f32 products) and
+    k_ista_b3 (split-bf16), both within 1e-5 of the oracle and within 1e-6 of each other.  nb = 130
+    gives the 128-block workgroups of k_ista_res a second, ragged one and the 64-block workgroups of
+    the split kernels a third."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from lrspnp import ops
+    from lrspnp.data import synthetic_dictionary
+    rng = np.random.default_rng(12)
+    nb, n = 130, 64
+    D = synthetic_dictionary(n, 256, 0)
+    Yb = (rng.standard_normal((nb, n)) * 0.3).astype(np.float32)
+    obs = (rng.random((nb, n)) > 0.1).astype(np.uint8)
+    Yb[obs == 0] = 0
+    Dd, Yd, od = (torch.from_numpy(a).cuda() for a in (D, Yb, obs))
+    alpha, thr = ops.ista_alpha(Dd, od, n, ops.ALPHA_SOFT, 0.1)
+    al, th = alpha.cpu().numpy(), thr.cpu().numpy()
+    coefs_o, phi_o = O.ista_batch(Yb, obs, D, al, th, 10, O.PROX_SOFT)
+    out = {}
+    for prec in (0, 1):
+        phi, coefs = ops.ista(Yd, od, Dd, n, alpha, thr, 10, ops.PROX_SOFT, want_coefs=True, precision=prec)
+        torch.cuda.synchronize()
+        out[prec] = (phi.cpu().numpy()[:, :n], coefs.cpu().numpy())
+        assert rel(out[prec][0], phi_o) < 1e-5 and rel(out[prec][1], coefs_o) < 1e-5
+    assert rel(out[1][0], out[0][0]) < 1e-6
+
+
 def test_nlm_matlab_prox_bitexact(ops):
     """lrs_nlm_matlab_col_f32 (NLmeansfilter.m closed form, fp64; the prox of the row-split ISTA
     kernel) against the oracle's C restatement at several h (including h where the exp weights are
