@@ -361,7 +361,7 @@ int lrs_image_to_unfolded_f32(const float *img, int64_t H, int64_t W, int64_t B,
  * step. */
 typedef struct {
     int32_t count, size, patience, wait, stop, stop_epoch, best_epoch, reserved;
-    double best, var_acc, last_var;
+    double best, var_acc, last_var;   /* var_acc: unused (lrs_es_init zeroes it); kept for the layout */
 } lrs_es_state;
 size_t lrs_es_ring_bytes(int size, int64_t N);
 int lrs_es_init(lrs_es_state *st, int size, int patience, void *stream);

@@ -547,9 +547,9 @@ struct S3Smem {
 static_assert(sizeof(S3Tile) * 2 >= 4 * 32 * 68 * sizeof(float), "epilogue staging fits the operand images");
 
 // One workgroup of the split-bf16 GEMM.  (gx, gy, gz): the GEMM's own grid (N tiles, M tiles, classes x
-// split-K); L: this workgroup's linear index in it.  L must keep the hardware's XCD (L % 8) of the
-// launch's workgroup: k_gemm_s3 passes its own index; k_gemm_s3x2 offsets its second GEMM by a
-// multiple of 8.
+// split-K); L: this workgroup's linear index in it, which the hardware deals to XCD L % 8.
+// (Kept apart from k_gemm_s3, its only caller: written into the kernel, the same statements compile to
+// different code in every instantiation -- other register counts in five.)
 template <class LA, class LB>
 __device__ __forceinline__ void gemm_s3_body(const GemmArgs &g, LA la, LB lb, S3Smem &sm, int L, unsigned gx,
                                              unsigned gy, unsigned gz) {
@@ -765,24 +765,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_s3(GemmArgs g, LA la, LB lb) {
                  gridDim.z);
 }
 
-// Two independent GEMMs in ONE launch (a conv's data gradient and its weight gradient, which read the
-// same dL/dz): a 1-D grid of round_up(T1, 8) + T2 workgroups, the first GEMM's tiles first (they are
-// dispatched first: the data gradient is the critical chain), the padding workgroups leave at once.
-struct S3Grid {
-    unsigned x, y, z;
-};
-template <class LA1, class LB1, class LA2, class LB2>
-__global__ __launch_bounds__(256, 2) void k_gemm_s3x2(GemmArgs g1, LA1 la1, LB1 lb1, S3Grid d1, GemmArgs g2, LA2 la2,
-                                                       LB2 lb2, S3Grid d2) {
-    __shared__ __attribute__((aligned(16))) S3Smem sm;
-    const int T1 = (int)(d1.x * d1.y * d1.z), T1p = (T1 + 7) & ~7, L = blockIdx.x;
-    if (L < T1p) {
-        if (L < T1) gemm_s3_body(g1, la1, lb1, sm, L, d1.x, d1.y, d1.z);
-    } else {
-        gemm_s3_body(g2, la2, lb2, sm, L - T1p, d2.x, d2.y, d2.z);
-    }
-}
-
 // ---- pointwise (1x1, stride 1, unpadded) conv product -----------------------------------------
 // C[M][N] (+)= A[M][Kp] B[K][N] (+ bias[M]) for M <= 256 output channels over N pixels: the
 // forward (A = the k_wprep forward planes WF, B = x) and the data gradient (A = WD = W^T planes,
@@ -802,7 +784,6 @@ struct PwArgs {
     float *C;
     const float *bias;
     int M, Kp32, ldsrow, accum;
-    int dbg;   // diagnostics only (LRS_PW_DBG): 1 no C stores, 2 no A loads, 4 no B loads
     int act;   // activation applied after the bias (a conv without BN: its act in the epilogue)
     // the masked-MSE head fused into the network's last conv (tgt != NULL; k_mse_head's arithmetic per
     // element): gz = act'(out) * (-norm (tgt m - out m) m) stored beside out, and per output row the
@@ -841,7 +822,7 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int64_t so = (int64_t)(8 * c + u) * a.N * 4;
-                v[i][u] = (c < nck && !(a.dbg & 4)) ? s3_bload(rs, voff, so < kOob ? (int)so : kOob) : 0.0f;
+                v[i][u] = c < nck ? s3_bload(rs, voff, so < kOob ? (int)so : kOob) : 0.0f;
             }
         }
 #pragma unroll
@@ -873,7 +854,7 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int64_t so = (int64_t)(8 * c + u) * a.N * 4;
-                v[j][u] = (it < items && !(a.dbg & 4)) ? s3_bload(rs, voff, so < kOob ? (int)so : kOob) : 0.0f;
+                v[j][u] = it < items ? s3_bload(rs, voff, so < kOob ? (int)so : kOob) : 0.0f;
             }
         }
 #pragma unroll
@@ -908,7 +889,7 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
             const int row = 16 * wv + 64 * j + jl;
-            const int vo = (row < a.M && k < a.lda && !(a.dbg & 2)) ? 2 * (row * a.lda + k) : kOob;
+            const int vo = (row < a.M && k < a.lda) ? 2 * (row * a.lda + k) : kOob;
 #pragma unroll
             for (int p = 0; p < 3; ++p)
                 f[j][p] = __builtin_bit_cast(s3bf8, __builtin_amdgcn_raw_buffer_load_b128(ra, vo, (int)(2 * p * a.pstride), 0));
@@ -967,7 +948,7 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
             const int idx = lane + 64 * i, rr = idx / (4 * NB), q = 4 * (idx % (4 * NB));
             const int m = 16 * wv + 64 * j + rr;
             const int64_t n = n0 + q;
-            if (m >= a.M || (a.dbg & 1)) continue;
+            if (m >= a.M) continue;
             float4 v = *reinterpret_cast<const float4 *>(E + rr * ES + q);
             const float bs = a.bias ? a.bias[m] : 0.0f;
             float *c = a.C + (int64_t)m * a.N + n;

@@ -163,140 +163,8 @@ __global__ __launch_bounds__(kGemmThreads) void k_gemm(GemmArgs g) {
         }
 }
 
-// ---- split-bf16 variant of the 128x128 GEMM (BK 32) ---------------------------------------------
-// Same tiling and pipeline as k_gemm, but the products run on v_mfma_f32_16x16x32_bf16: every fp32
-// operand is split exactly into three bf16 terms (hi + mid + lo) when its fragment leaves LDS and
-// the six partial products with i + j <= 4 are accumulated in fp32 (the dropped ones are <= 2^-24
-// relative: fp32-GEMM accuracy, the ISTA kernel's scheme).  2.7x fewer matrix-core cycles than the
-// f32 MFMA for the same tile.
-constexpr int kBK32 = 32, kLdsK32 = kBK32 + 4;
-typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
-
-template <bool KCONTIG>
-__device__ __forceinline__ void load_tile32(const float *__restrict__ S, int ld, int k0, int kend, int x0, int X,
-                                            float4 (&r)[4]) {
-    const int t = threadIdx.x;
-    float v[16];
-    if (KCONTIG) {
-        const int x = x0 + (t >> 1), kb = k0 + 16 * (t & 1);
-        const float *src = S + (int64_t)x * ld;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = (x < X && kb + u < kend) ? src[kb + u] : 0.0f;
-    } else {
-        const int x = x0 + (t & 127), kb = k0 + 16 * (t >> 7);
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = (x < X && kb + u < kend) ? S[(int64_t)(kb + u) * ld + x] : 0.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) r[q] = float4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-}
-
-__device__ __forceinline__ void store_tile32(float (*T)[kLdsK32], const float4 (&r)[4], bool kcontig) {
-    const int t = threadIdx.x;
-    const int x = kcontig ? (t >> 1) : (t & 127);
-    const int kb = kcontig ? 16 * (t & 1) : 16 * (t >> 7);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(&T[x][kb + 4 * q]) = r[q];
-}
-
-__device__ __forceinline__ void gsplit8(const float4 &a, const float4 &b, gbf16x8 (&f)[3]) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h = (__bf16)v[e];
-        const float r1 = v[e] - (float)h;
-        const __bf16 m = (__bf16)r1;
-        f[0][e] = h;
-        f[1][e] = m;
-        f[2][e] = (__bf16)(r1 - (float)m);
-    }
-}
-
-__device__ __forceinline__ floatx4 gmfma6(const gbf16x8 (&A)[3], const gbf16x8 (&B)[3], floatx4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[2], B[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[0], acc, 0, 0, 0);
-    return acc;
-}
-
-template <int TA, int TB>
-__global__ __launch_bounds__(kGemmThreads) void k_gemm_b3(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) float As[2][kBM][kLdsK32];
-    __shared__ __attribute__((aligned(16))) float Bs[2][kBN][kLdsK32];
-    const int m0 = blockIdx.y * kBM, n0 = blockIdx.x * kBN;
-    const int kbeg = blockIdx.z * g.kchunk;
-    const int kend = min(g.K, kbeg + g.kchunk);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int wm = (wv >> 1) * 64, wn = (wv & 1) * 64;
-    const int jl = lane & 15, gk = lane >> 4;
-    const int lda = TA ? g.M : g.K;
-    const int ldb = TB ? g.K : g.N;
-    floatx4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-    float4 ra[4], rb[4];
-    load_tile32<TA == 0>(g.A, lda, kbeg, kend, m0, g.M, ra);
-    load_tile32<TB == 1>(g.B, ldb, kbeg, kend, n0, g.N, rb);
-    int stage = 0;
-    store_tile32(As[0], ra, TA == 0);
-    store_tile32(Bs[0], rb, TB == 1);
-    __syncthreads();
-    for (int k0 = kbeg; k0 < kend; k0 += kBK32) {
-        const bool more = k0 + kBK32 < kend;
-        if (more) {
-            load_tile32<TA == 0>(g.A, lda, k0 + kBK32, kend, m0, g.M, ra);
-            load_tile32<TB == 1>(g.B, ldb, k0 + kBK32, kend, n0, g.N, rb);
-        }
-        // fragments: 8 consecutive k (8 gk .. 8 gk + 7) of row / column 16 a + jl
-        gbf16x8 fb[4][3];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const float *src = &Bs[stage][wn + 16 * b + jl][8 * gk];
-            gsplit8(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 4), fb[b]);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            gbf16x8 fa[3];
-            const float *src = &As[stage][wm + 16 * a + jl][8 * gk];
-            gsplit8(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 4), fa);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = gmfma6(fa, fb[b], acc[a][b]);
-        }
-        if (more) {
-            store_tile32(As[stage ^ 1], ra, TA == 0);   // the other stage: last read one step ago
-            store_tile32(Bs[stage ^ 1], rb, TB == 1);
-        }
-        __syncthreads();
-        stage ^= 1;
-    }
-    float *C = g.C + (int64_t)blockIdx.z * g.M * g.N;
-    const bool final_out = gridDim.z == 1;
-    const float dv = (final_out && g.div) ? *g.div : 1.0f;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int n = n0 + wn + 16 * b + jl;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm + 16 * a + 4 * gk + r;
-                if (m < g.M && n < g.N) {
-                    float v = acc[a][b][r];
-                    if (final_out) {
-                        if (g.bias) v = v + g.bias[m];
-                        if (g.div) v = v / dv;
-                        if (g.accum) v = C[(int64_t)m * g.N + n] + v;
-                    }
-                    C[(int64_t)m * g.N + n] = v;
-                }
-            }
-        }
-}
+// k-step of the split-bf16 128x128 GEMM (k_gemm_s3, dip_gemm.h): choose_split rounds its k-chunks to it
+constexpr int kBK32 = 32;
 
 // ---- small-tile variant (64x64, BK 16, 2x2 waves of 32x32) for GEMMs whose 128-tile grid is
 // too small to fill the chip (the 36x36 native U-Net layers) ----------------------------------
@@ -1105,8 +973,6 @@ constexpr int kBnRegMaxQ = 10;   // 40960 pixels
 
 template <int NQ>
 __device__ __forceinline__ bool bnr_ok(int P, int u) { return threadIdx.x + u * kBn1Threads < (unsigned)(P >> 2); }
-template <int TH>
-__device__ __forceinline__ bool bnr_ok_t(int P, int u) { return threadIdx.x + u * TH < (unsigned)(P >> 2); }
 
 // quad q of a [C][P] tensor at channel offset off, summed over nsplit split-K partials (stride MN):
 // acc[e] = the splits e, e + 8, ... in increasing order (k_gemm_reduce's order); the loads of one
@@ -1137,13 +1003,11 @@ __device__ __forceinline__ float4 splitk_sum4(const float *__restrict__ part, in
 
 // forward: z = (split-K partials summed in k_gemm_reduce's order + bias) or z as stored; then
 // BN statistics, normalisation, affine (Lipschitz rescale), activation.  part == nullptr: z given.
-// TH = threads per workgroup (quads t + TH u): 1024 by default; 256 (4 wave slots instead of 16) lets a
-// 98^2 map's workgroup fit where one sparse-coding workgroup retires (tuning build, LRS_DIP_BNR_SMALL_WG)
 // sdiv (nullable): the conv ran on the raw weights W_bar (the spectral-norm scale not yet known when
 // it was launched, dipnet_step's overlapped sigma): z = sum / scale + bias, the same order as the
 // scaled path's epilogue (W / scale) x + bias up to the rounding of the quotient's place.
-template <int NQ, int TH = kBn1Threads>
-__global__ __launch_bounds__(TH) void k_bn_fwd_r(const float *__restrict__ part, int nsplit,
+template <int NQ>
+__global__ __launch_bounds__(kBn1Threads) void k_bn_fwd_r(const float *__restrict__ part, int nsplit,
                                                  const float *__restrict__ bias, BnArgs a,
                                                  const float *__restrict__ sdiv = nullptr) {
     __shared__ double red[2 * kBn1Threads / 64];
@@ -1155,8 +1019,8 @@ __global__ __launch_bounds__(TH) void k_bn_fwd_r(const float *__restrict__ part,
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
         zv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (!bnr_ok_t<TH>(a.P, u)) continue;
-        const int q = t + u * TH;
+        if (!bnr_ok<NQ>(a.P, u)) continue;
+        const int q = t + u * kBn1Threads;
         if (!part) {
             zv[u] = z4[q];
             continue;
@@ -1188,7 +1052,7 @@ __global__ __launch_bounds__(TH) void k_bn_fwd_r(const float *__restrict__ part,
     double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int u = 0; u < NQ; ++u)
-        if (bnr_ok_t<TH>(a.P, u)) {
+        if (bnr_ok<NQ>(a.P, u)) {
             const double d0 = (double)zv[u].x - K, d1 = (double)zv[u].y - K, d2 = (double)zv[u].z - K,
                          d3 = (double)zv[u].w - K;
             s1 += d0; s2 += d0 * d0;
@@ -1203,9 +1067,9 @@ __global__ __launch_bounds__(TH) void k_bn_fwd_r(const float *__restrict__ part,
     float4 *y4 = reinterpret_cast<float4 *>(a.y + off);
 #pragma unroll
     for (int u = 0; u < NQ; ++u)
-        if (bnr_ok_t<TH>(a.P, u)) {
+        if (bnr_ok<NQ>(a.P, u)) {
             const float4 v = zv[u];
-            y4[t + u * TH] =
+            y4[t + u * kBn1Threads] =
                 make_float4(act_fwd((v.x - m32) * is32 * gm + bt, a.act), act_fwd((v.y - m32) * is32 * gm + bt, a.act),
                             act_fwd((v.z - m32) * is32 * gm + bt, a.act), act_fwd((v.w - m32) * is32 * gm + bt, a.act));
         }
@@ -1998,10 +1862,6 @@ __global__ void k_adam(float *__restrict__ p, const float *__restrict__ g, float
     }
 }
 
-__global__ void k_counter_inc(int *c) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *c += 1;
-}
-
 __global__ void k_step_begin(double *loss_acc, int *step) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         *loss_acc = 0.0;
@@ -2079,36 +1939,7 @@ __global__ __launch_bounds__(256) void k_es_step(const float *__restrict__ out, 
     }
 }
 
-#ifdef LRS_TUNING
-// The round-5 form (tuning build, LRS_DIP_ES_TWO_PASS=1, A/B only): push, then the whole ring read
-// twice per step (mean, then squared deviations), workgroup sums into var_acc by atomics.
-__global__ void k_es_push_r5(const float *__restrict__ out, int64_t N, float *__restrict__ ring, lrs_es_state *st) {
-    const int slot = st->count % st->size;
-    float *dst = ring + (int64_t)slot * N;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = out[i];
-}
-__global__ void k_es_var_r5(const float *__restrict__ ring, int64_t N, lrs_es_state *st) {
-    __shared__ double red[8];
-    if (st->count + 1 < st->size) return;
-    const int S = st->size;
-    double s = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-        double ave = 0.0;
-        for (int j = 0; j < S; ++j) ave += (double)ring[(int64_t)j * N + i];
-        ave /= S;
-        for (int j = 0; j < S; ++j) {
-            const double d = ave - (double)ring[(int64_t)j * N + i];
-            s += d * d;
-        }
-    }
-    s = block_sum_d(s, red);
-    if (threadIdx.x == 0) atomicAdd(&st->var_acc, s);
-}
-#endif
-
 // one wave: the nblk partials of k_es_step in a fixed order, then the reference's patience test
-// (nblk == 0: the round-5 form's var_acc instead)
 __global__ void k_es_decide(const float *ring, int64_t N, int nblk, lrs_es_state *st) {
     const int S = st->size;
     double *part = reinterpret_cast<double *>(reinterpret_cast<char *>(const_cast<float *>(ring)) + es_ab_offset_bytes(S, N)) + N;
@@ -2121,16 +1952,10 @@ __global__ void k_es_decide(const float *ring, int64_t N, int nblk, lrs_es_state
     dq = wave_sum_d(dq);   // fixed order
     qa = wave_sum_d(qa);
     if (threadIdx.x != 0) return;
-    double v;
-    if (nblk == 0) {
-        v = st->var_acc;
-    } else {
-        const int c = st->count;
-        const double q = (c == 0 || es_refresh(c, S)) ? dq : *q2 + dq;
-        *q2 = q;
-        v = q - qa / (double)S;
-    }
     const int epoch = st->count;           // iteration index i of the reference loop
+    const double q = (epoch == 0 || es_refresh(epoch, S)) ? dq : *q2 + dq;
+    *q2 = q;
+    const double v = q - qa / (double)S;
     st->count += 1;
     if (st->count >= S && !st->stop) {
         const double var = v / (double)N / (double)S;
@@ -2147,7 +1972,6 @@ __global__ void k_es_decide(const float *ring, int64_t N, int nblk, lrs_es_state
             }
         }
     }
-    st->var_acc = 0.0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2160,28 +1984,8 @@ struct CatGeom {
     int oay, oax, oby, obx;            // crop offsets into a and into up2(b)
 };
 
-__global__ void k_concat_fwd(const float *__restrict__ a, const float *__restrict__ b, CatGeom g,
-                             float *__restrict__ out) {
-    const int64_t HW = (int64_t)g.H * g.W, n = (int64_t)(g.Ca + g.Cb) * HW;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i / HW);
-        const int p = (int)(i - (int64_t)c * HW);
-        const int y = p / g.W, x = p - y * g.W;
-        float v;
-        if (c < g.Ca) {
-            v = a[((int64_t)c * g.Ha + y + g.oay) * g.Wa + x + g.oax];
-        } else {
-            int yy = y + g.oby, xx = x + g.obx;
-            if (g.upb) { yy >>= 1; xx >>= 1; }
-            v = b[((int64_t)(c - g.Ca) * g.Hb + yy) * g.Wb + xx];
-        }
-        out[i] = v;
-    }
-}
-
-// The same copies / sums laid out for throughput: grid (row quads, channels), a thread = 4
-// consecutive x of one row of one channel; no 64-bit division per element, float4 stores when the
-// rows are multiples of 4 (the values and the 2x2 summation order are k_concat_fwd / _bwd's).
+// Forward: grid (row quads, channels), a thread = 4 consecutive x of one row of one channel; no 64-bit
+// division per element, float4 stores when the rows are multiples of 4.
 __global__ __launch_bounds__(256) void k_concat_fwd4(const float *__restrict__ a, const float *__restrict__ b,
                                                      CatGeom g, float *__restrict__ out) {
     const int W4 = (g.W + 3) >> 2;
@@ -2214,6 +2018,8 @@ __global__ __launch_bounds__(256) void k_concat_fwd4(const float *__restrict__ a
     }
 }
 
+// Backward: the output gradient gathered back (zeros outside the crop; the 2x2 children of an
+// upsampled b pixel are summed, dy then dx); acc: accumulate onto gx.
 // part 0: ga over (Ha rows x Wa), channels Ca; part 1: gb over (Hb x Wb), channels Cb
 __global__ __launch_bounds__(256) void k_concat_bwd4(const float *__restrict__ go, CatGeom g, float *__restrict__ gx,
                                                      int acc, int part) {
@@ -2258,42 +2064,6 @@ __global__ __launch_bounds__(256) void k_concat_bwd4(const float *__restrict__ g
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (X0 + e < Ws) dst[e] = acc ? dst[e] + v[e] : v[e];
-    }
-}
-
-// ga (nullable) / gb (nullable): gather the output gradient back (zeros outside the crop;
-// the 2x2 children of an upsampled b pixel are summed); accumulate flags per input
-__global__ void k_concat_bwd(const float *__restrict__ go, CatGeom g, float *__restrict__ ga, int acc_a,
-                             float *__restrict__ gb, int acc_b) {
-    const int64_t HW = (int64_t)g.H * g.W;
-    const int64_t na = ga ? (int64_t)g.Ca * g.Ha * g.Wa : 0;
-    const int64_t nb = gb ? (int64_t)g.Cb * g.Hb * g.Wb : 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        if (i < na) {
-            const int64_t hw = (int64_t)g.Ha * g.Wa;
-            const int c = (int)(i / hw);
-            const int p = (int)(i - (int64_t)c * hw);
-            const int y = p / g.Wa - g.oay, x = p % g.Wa - g.oax;
-            float v = 0.0f;
-            if (y >= 0 && y < g.H && x >= 0 && x < g.W) v = go[(int64_t)c * HW + (int64_t)y * g.W + x];
-            ga[i] = acc_a ? ga[i] + v : v;
-        } else {
-            const int64_t j = i - na;
-            const int64_t hw = (int64_t)g.Hb * g.Wb;
-            const int c = (int)(j / hw);
-            const int p = (int)(j - (int64_t)c * hw);
-            const int Y = p / g.Wb, X = p % g.Wb;
-            const float *gc = go + (int64_t)(g.Ca + c) * HW;
-            float v = 0.0f;
-            const int f = g.upb ? 2 : 1;
-            for (int dy = 0; dy < f; ++dy)
-                for (int dx = 0; dx < f; ++dx) {
-                    const int y = Y * f + dy - g.oby, x = X * f + dx - g.obx;
-                    if (y >= 0 && y < g.H && x >= 0 && x < g.W) v += gc[(int64_t)y * g.W + x];
-                }
-            gb[j] = acc_b ? gb[j] + v : v;
-        }
     }
 }
 

@@ -6,7 +6,6 @@
 // step in a hipGraph and replay it: the Adam step count and the early-stopping state live in
 // device memory, so a replayed step is exactly the eager step.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -25,27 +24,6 @@ namespace {
 
 constexpr int kEw = 256;   // elementwise block size
 constexpr int64_t kForkBigP = 9604;   // sigma beside the first conv: only where that conv's map is >= 98^2
-
-// A/B tuning knobs.  The environment is read only by the tuning build (make TUNING=1 ->
-// liblrspnp_hip_tune.so, -DLRS_TUNING); the product library always takes the default, so a
-// variable left set on a production box cannot change its arithmetic path.
-inline int64_t tune_knob(const char *name, int64_t dflt) {
-#ifdef LRS_TUNING
-    const char *e = getenv(name);
-    return e ? atoll(e) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
-inline const char *tune_str(const char *name) {
-#ifdef LRS_TUNING
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
 
 inline unsigned ew_blocks(int64_t n, int64_t cap = 4096) {
     int64_t b = (n + kEw - 1) / kEw;
@@ -101,6 +79,11 @@ struct Split {
     bool big;   // 128x128 tiles (k_gemm) or 64x64 (k_gemm64)
 };
 
+constexpr int64_t kSplitMinTiles = 256;   // choose_split splits K below this many tiles
+// ... into at most this many splits (a deep K: 256).  196^2 step, 2 rounds: 32 -> 1.327 ms, 64 -> 1.265,
+// 128 -> 1.279, 256 -> 1.285; profiles/r04/split_cap/
+constexpr int kSplitCap = 64;
+
 // Tile choice and split-K: 128x128 tiles when they alone give >= 64 workgroups, else 64x64;
 // then split K until ~512 workgroups (2 per CU), keeping >= 128 of K per split and <= 64 splits.
 // (Measured with the f32 kernels: 128-tiles with deeper split-K on the small-N weight-gradient
@@ -116,16 +99,11 @@ Split choose_split(int M, int N, int K, int precision = LRS_DIP_SPLIT_BF16, bool
     const bool big = force_big || t128 >= 64 || (precision == LRS_DIP_SPLIT_BF16 && K >= 8192 && t128 >= 4) || deep;
     const int64_t tiles = big ? t128 : (int64_t)((M + kBM64 - 1) / kBM64) * ((N + kBN64 - 1) / kBN64);
     int S = 1;
-    // split-K below this many tiles (LRS_DIP_SPLIT_MIN_TILES, tuning only)
-    static const int64_t min_tiles = tune_knob("LRS_DIP_SPLIT_MIN_TILES", 256);
-    if (tiles < min_tiles) {
+    if (tiles < kSplitMinTiles) {
         S = (int)((target + tiles - 1) / tiles);   // ~2 workgroups per CU (256 and 1024 measured slower)
         const int smax = deep ? K / 512 : (K + 127) / 128;
         if (S > smax) S = smax;
-        // at most 64 splits otherwise (LRS_DIP_SPLIT_CAP, tuning only; 196^2 step, 2 rounds:
-        // 32 -> 1.327 ms, 64 -> 1.265, 128 -> 1.279, 256 -> 1.285; profiles/r04/split_cap/)
-        static const int cap = (int)std::max<int64_t>(1, tune_knob("LRS_DIP_SPLIT_CAP", 64));
-        if (S > (deep ? 256 : cap)) S = deep ? 256 : cap;
+        if (S > (deep ? 256 : kSplitCap)) S = deep ? 256 : kSplitCap;
         if (S < 1) S = 1;
     }
     const int bk = (big && precision == LRS_DIP_SPLIT_BF16) ? kBK32 : kBK;
@@ -210,33 +188,23 @@ inline int r16(int x) { return (x + 15) & ~15; }
 // beside that layer's weight gradient anyway, and it adds a split-K reduce and the border launches
 // to the critical chain.  lrs_dip_opts::upsample_dgrad = 1 selects it (tests cover both).
 // An upsampled, reflection-padded 3 x 3 stride-1 conv runs by output parity class in the network
-// engine (dip_gemm.h LdUpFwdTM / LdUpDgradTM, 4/9 of the direct products).  LRS_DIP_UPC=0 keeps the
-// direct implicit GEMM over the upsampled grid (A/B only).
+// engine (dip_gemm.h LdUpFwdTM / LdUpDgradTM, 4/9 of the direct products); every other upsampled conv
+// keeps the direct implicit GEMM over the upsampled grid.
 inline bool upc_conv(const ConvGeom &g) {
-    static const bool on = tune_knob("LRS_DIP_UPC", 1) != 0;
-    return on && g.up && g.k == 3 && g.pad == 1 && g.pad_mode == LRS_PAD_REFLECT && g.stride == 1 && g.Hs >= 2 &&
-           g.Ws >= 2;
+    return g.up && g.k == 3 && g.pad == 1 && g.pad_mode == LRS_PAD_REFLECT && g.stride == 1 && g.Hs >= 2 && g.Ws >= 2;
 }
 
 // fixed with the geometry (make_geom, lrs_dip_opts::upsample_dgrad): the workspace size, the
 // weight-preparation table and the backward all read this one value
 inline int up_eff_k(const ConvGeom &g) { return g.ke; }
 // ---- small-map convs on k_conv_sm (dip_sm.h) ------------------------------------------------
-// A conv runs there when it is not 1x1, k <= 3 and its output map is below implicit_min_pixels()
-// (the maps that had the explicit im2col path).  LRS_DIP_SM=0 keeps the explicit path (A/B only).
-inline bool sm_enabled() {
-    static const bool v = tune_knob("LRS_DIP_SM", 1) != 0;
-    return v;
-}
+// A split-bf16 conv runs there when it is not 1x1, k <= 3 and its output map is below kImplicitMinP
+// (the maps that had the explicit im2col path).
 
-// 64 x 64 tiles; split K so that the grid has ~sm_target() workgroups (k per split a multiple of
-// 64).  LRS_DIP_SM_WG overrides the target (tuning only).
-inline int64_t sm_target() {
-    static const int64_t v = std::max<int64_t>(1, tune_knob("LRS_DIP_SM_WG", 640));
-    return v;
-}
+// 64 x 64 tiles; split K so that the grid has ~kSmTargetWg workgroups (k per split a multiple of 64).
+constexpr int64_t kSmTargetWg = 640;
 Split sm_split(int M, int N, int K) {
-    const int64_t T = (int64_t)((M + 63) / 64) * ((N + 63) / 64), W = sm_target();
+    const int64_t T = (int64_t)((M + 63) / 64) * ((N + 63) / 64), W = kSmTargetWg;
     int64_t kc = round_up(std::max<int64_t>(1, ((int64_t)K * T + W - 1) / W), kSmK);
     if (kc > K) kc = round_up(K, kSmK);
     int S = (int)((K + kc - 1) / kc);
@@ -389,18 +357,13 @@ inline int64_t wprep_elems(const ConvGeom &g, int Cout) {
 // split-K workgroup target of a forward conv whose partials a fused BN kernel finishes: fewer
 // splits than the GEMMs' 512 (the BN kernel, one workgroup per channel, re-reads every partial):
 // 196^2 step 1.336 -> 1.312 ms at 384 (A/B on one box: 256 1.317, 320 1.313).  The workspace is
-// sized for 512, so a larger LRS_DIP_FWD_SPLIT_WG (tuning only) fails with LRS_E_WORKSPACE.
-inline int fwd_split_target() {
-    static const int v = (int)std::max<int64_t>(1, tune_knob("LRS_DIP_FWD_SPLIT_WG", 384));
-    return v;
-}
+// sized for 512, so a larger target fails with LRS_E_WORKSPACE.
+constexpr int kFwdSplitWg = 384;
 
 // Split target of the padded-domain data-gradient GEMMs whose split-K partials k_fold_pad sums
-// (every partial is re-read by the fold, as by the forward BN kernels above).
-inline int dgrad_split_target() {
-    static const int v = (int)std::max<int64_t>(1, std::min<int64_t>(512, tune_knob("LRS_DIP_DGRAD_SPLIT_WG", 512)));
-    return v;
-}
+// (every partial is re-read by the fold, as by the forward BN kernels above); at most the 512 the
+// workspace is sized for.
+constexpr int kDgradSplitWg = 512;
 
 template <class LA, class LB>
 int gemm_s3_conv(const LA &la, const LB &lb, float *C, const float *bias, const float *div, int M, int N, int K,
@@ -431,7 +394,7 @@ int upc_fwd(const ConvGeom &g, const float *x, const __bf16 *wpre, const float *
             int64_t part_cap, hipStream_t st, int *nsplit_out) {
     const int Cp = r16(g.Cin), Q = g.Hs * g.Ws, K = 4 * Cp;
     const int64_t P = (int64_t)g.Ho * g.Wo;
-    const Split s = choose_split(Cout, 4 * Q, K, LRS_DIP_SPLIT_BF16, true, nsplit_out ? fwd_split_target() : 512);
+    const Split s = choose_split(Cout, 4 * Q, K, LRS_DIP_SPLIT_BF16, true, nsplit_out ? kFwdSplitWg : 512);
     if (nsplit_out) *nsplit_out = s.S;
     GemmArgs a{nullptr, nullptr, y, bias, nullptr, Cout, Q, K, s.kchunk, 0, 4, g.Ws, g.Wo, P};
     if (s.S > 1) {
@@ -458,7 +421,7 @@ int upc_dgrad(const ConvGeom &g, const float *gz, const __bf16 *wd, int Cout, fl
     int nsplit = 1;   // split-K partials are summed inside the fold
     int rc = gemm_s3_conv(LdPre{wd, (int64_t)g.Cin * K, K, g.Cin}, LdUpDgradTM{gz, Cout * g.Ho * g.Wo * 4, g, Cout, Cop, nullptr},
                           gxe, nullptr, nullptr, g.Cin, Qe, K, part, part_cap, st, &nsplit, 0,
-                          dgrad_split_target());
+                          kDgradSplitWg);
     if (rc) return rc;
     ConvGeom fg = g;
     fg.up = 0;
@@ -503,11 +466,7 @@ inline bool conv_implicit_ok(const ConvGeom &g, int Cout) {
 // today: 2048 -> 1024 moves the 36^2 maps (1296 pixels) to the implicit paths, 36^2 step 0.652 ->
 // 0.638 ms, and the skip net's 32^2 maps, 512^2 step 9.27 -> 9.23 ms; 512 (the 196^2 net's 25^2 maps
 // too) is slower there, 1.244 -> 1.288 ms (profiles/r04/implicit_min_p/).
-// LRS_DIP_IMPLICIT_MIN_P overrides (tuning only).
-inline int64_t implicit_min_pixels() {
-    static const int64_t v = tune_knob("LRS_DIP_IMPLICIT_MIN_P", 1024);
-    return v;
-}
+constexpr int64_t kImplicitMinP = 1024;
 
 // split w into the bf16 planes of the forward operand (and of the data-gradient one if wd)
 int wprep(const ConvGeom &g, const float *w, int Cout, __bf16 *wf, __bf16 *wd, hipStream_t st) {
@@ -519,17 +478,11 @@ int wprep(const ConvGeom &g, const float *w, int Cout, __bf16 *wf, __bf16 *wd, h
     return LRS_OK;
 }
 
-// LRS_DIP_PW_NB = the allowed NB digits, e.g. "4" keeps 64-pixel workgroups everywhere (A/B only)
-inline bool pw_nb_allowed(int nb) {
-    static const char *v = tune_str("LRS_DIP_PW_NB");
-    return !v || strchr(v, '0' + nb) != nullptr;
-}
-
 // k_pw instantiations: MT row blocks x NB 16-pixel column blocks, and the workgroups per CU their
 // registers allow (one wave per SIMD each; gfx950: 512 VGPRs per SIMD lane over the waves, in
 // granules of 8; the counts of the current build: 80, 150, 192, 234, 198).  48-pixel workgroups
-// (NB = 3) for the LDS-bound K = 198 data gradient measured ~10 us per 196^2 step slower (A/B,
-// LRS_DIP_PW_NB) and were dropped.
+// (NB = 3) for the LDS-bound K = 198 data gradient measured ~10 us per 196^2 step slower (A/B)
+// and were dropped.
 struct PwKernel {
     int mt, nb, wg_per_cu;
     void (*fn)(PwArgs);
@@ -560,13 +513,12 @@ int pw_launch(const __bf16 *A, int64_t pstride, int lda, int M, const float *B, 
     for (size_t i = 0; i < sizeof(kPwKernels) / sizeof(kPwKernels[0]); ++i)   // up to K = 256: 3 x 80 x 528 B
         if (const int rc = lds_opt_in((const void *)kPwKernels[i].fn, 3 * 80 * pw_ldsrow(256), attr_set[i])) return rc;
     if (Kp32 > 256 || (int64_t)K * N * 4 >= kOob || 3 * pstride * 2 >= kOob) return LRS_E_UNSUPPORTED;
-    static const int dbg = (int)tune_knob("LRS_PW_DBG", 0);
-    const PwArgs a{A, pstride, lda, B, K, N, C, bias, M, Kp32, ldsrow, accum, dbg, act};
+    const PwArgs a{A, pstride, lda, B, K, N, C, bias, M, Kp32, ldsrow, accum, act};
     const int mt = (M + 63) / 64;
     const PwKernel *best = nullptr;
     int64_t best_cost = 0;
     for (const PwKernel &k : kPwKernels) {
-        if (k.mt != mt || !pw_nb_allowed(k.nb)) continue;
+        if (k.mt != mt) continue;
         const int lds = 3 * 16 * k.nb * ldsrow;
         const int per_cu = std::min(k.wg_per_cu, (160 * 1024) / lds);
         const int64_t wgs = (N + 16 * k.nb - 1) / (16 * k.nb);
@@ -612,7 +564,7 @@ int conv_fwd(const ConvGeom &g, const float *x, const float *w, const float *bia
         const int kk = g.k * g.k, Cp = r16(g.Cin);
         return gemm_s3_conv(LdPre{wpre, (int64_t)Cout * kk * Cp, kk * Cp, Cout},
                             LdFwdTM{x, g.Cin * g.Hs * g.Ws * 4, g, Cp, nullptr}, y, bias, nullptr, Cout, P, kk * Cp,
-                            part, part_cap, st, nsplit_out, 0, nsplit_out ? fwd_split_target() : 512);
+                            part, part_cap, st, nsplit_out, 0, nsplit_out ? kFwdSplitWg : 512);
     }
     if (!plain_unit(g)) {
         const dim3 grid((unsigned)((P + 255) / 256), (unsigned)std::min(Kc, 65535));
@@ -693,7 +645,7 @@ int conv_bwd(const ConvGeom &g, const float *gz, const float *col, const float *
         int nsplit = 1;   // split-K partials are summed inside the fold
         rc = gemm_s3_conv(LdPre{wd, (int64_t)g.Cin * kk * Cop, kk * Cop, g.Cin},
                           LdDgradTM{gz, Cout * P * 4, g, Cout, Cop, nullptr}, dcol, nullptr, nullptr, g.Cin, Qp,
-                          kk * Cop, part, part_cap, st, &nsplit, 0, dgrad_split_target());
+                          kk * Cop, part, part_cap, st, &nsplit, 0, kDgradSplitWg);
         if (rc) return rc;
         if (nsplit == 1 && !g.up && g.Ws % 4 == 0 && g.Cin <= 65535 && ((uintptr_t)gx & 15) == 0) {   // one partial: row quads
             const int q = g.Hs * (g.Ws / 4);
@@ -731,10 +683,8 @@ inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // Register-resident one-workgroup-per-channel BN (k_bn_fwd_r / k_bn_bwd_r): float4 quads per
 // thread for a channel of P pixels, or 0 where the S-way split / the P <= 4096 kernels are used.
-// LRS_DIP_BNREG_MAX_P overrides the upper limit (tuning only; 0 disables).
 inline int bn_reg_q(int64_t P, bool vec) {
-    static const int64_t maxp = tune_knob("LRS_DIP_BNREG_MAX_P", (int64_t)4 * kBn1Threads * kBnRegMaxQ);
-    if (!vec || P <= 4 * kBn1Threads || P > maxp || P > (int64_t)4 * kBn1Threads * kBnRegMaxQ) return 0;
+    if (!vec || P <= 4 * kBn1Threads || P > (int64_t)4 * kBn1Threads * kBnRegMaxQ) return 0;
     const int q = (int)((P + 4 * kBn1Threads - 1) / (4 * kBn1Threads));
     static const int qs[] = {2, 3, 4, 6, 8, 10};
     for (int v : qs)
@@ -744,20 +694,12 @@ inline int bn_reg_q(int64_t P, bool vec) {
 
 // Threads of a one-workgroup-per-channel BatchNorm kernel (k_reduce_bn1, k_reduce_bn_bwd1, k_bn_fwd1,
 // k_bn_bwd1): kBn1Small where the channel fits 2 values per thread of it (the 18^2 and smaller maps at
-// 36^2, the 13^2 ones at 196^2), else kBn1Threads.  A/B (tuning build, 2 rounds): 36^2 step 0.671 ->
+// 36^2, the 13^2 ones at 196^2), else kBn1Threads.  A/B (2 interleaved rounds): 36^2 step 0.671 ->
 // 0.657 ms with 256 threads up to 1024 pixels, but the 196^2 step 1.274 -> 1.280 (its 25^2 maps then
-// hold 3 values per thread).  LRS_DIP_BN1_SMALL = the pixel limit (0: 1024 threads everywhere).
-inline int bn1_threads(int64_t P) {
-    // (clamped to what a kBn1Small-thread kernel covers: 4 values per thread)
-    static const int64_t lim = std::min<int64_t>(tune_knob("LRS_DIP_BN1_SMALL", 2 * kBn1Small), 4 * kBn1Small);
-    return P <= lim ? kBn1Small : kBn1Threads;
-}
-
-// 98^2 maps' register BN forward on 256-thread workgroups (tuning build only; default off)
-inline bool bnr_small_wg() {
-    static const bool v = tune_knob("LRS_DIP_BNR_SMALL_WG", 0) != 0;
-    return v;
-}
+// hold 3 values per thread).  (A kBn1Small-thread kernel covers at most 4 values per thread.)
+constexpr int64_t kBn1SmallMaxP = 2 * kBn1Small;
+static_assert(kBn1SmallMaxP <= 4 * kBn1Small, "a kBn1Small-thread kernel holds 4 values per thread");
+inline int bn1_threads(int64_t P) { return P <= kBn1SmallMaxP ? kBn1Small : kBn1Threads; }
 
 #define LRS_BNR_SWITCH(nq, K, ...)                                                                \
     switch (nq) {                                                                                 \
@@ -815,6 +757,10 @@ int bn_bwd(const float *gy, const float *y, const float *z, const float *gamma, 
 // the n convs (blockIdx.y < n, k_sn_gram's body) and, in the extra row blockIdx.y == n, the first
 // conv's forward planes from the raw weights (the head ConvPrep) with the step's loss reset and Adam
 // step count: one launch instead of two.
+// kHeadPlaneRows: the first conv's planes on 8 grid rows of kSnSplit workgroups (one row: the kernel took
+// 36.7 us, its 16 plane workgroups the longest; 8 rows: 19.2 us, 196^2 step 1.194 -> 1.177 ms, 3 interleaved
+// rounds, profiles/r06/ab/head_plane_rows.txt)
+constexpr int kHeadPlaneRows = 8;
 __global__ __launch_bounds__(256) void k_sn_gram_head(const SnConv *convs, double *gram, int n, const ConvPrep *head,
                                                      double *loss_acc, int *step) {
     __shared__ float Ws[128][36];
@@ -864,16 +810,6 @@ __global__ void k_es_init(lrs_es_state *st, int size, int patience) {
 
 int es_update(const float *out, int64_t N, float *ring, lrs_es_state *es, hipStream_t st) {
     const unsigned nblk = ew_blocks(N, kEsMaxBlocks);
-#ifdef LRS_TUNING
-    static const bool two_pass = tune_knob("LRS_DIP_ES_TWO_PASS", 0) != 0;
-    if (two_pass) {
-        hipLaunchKernelGGL(k_es_push_r5, dim3(nblk), dim3(kEw), 0, st, out, N, ring, es);
-        hipLaunchKernelGGL(k_es_var_r5, dim3(nblk), dim3(kEw), 0, st, (const float *)ring, N, es);
-        hipLaunchKernelGGL(k_es_decide, dim3(1), dim3(64), 0, st, (const float *)ring, N, 0, es);
-        LRS_CHECK_LAUNCH();
-        return LRS_OK;
-    }
-#endif
     hipLaunchKernelGGL(k_es_step, dim3(nblk), dim3(kEw), 0, st, out, N, ring, es);
     hipLaunchKernelGGL(k_es_decide, dim3(1), dim3(64), 0, st, (const float *)ring, N, (int)nblk, es);
     LRS_CHECK_LAUNCH();
@@ -1067,7 +1003,7 @@ extern "C" int lrs_bn_act_bwd_f32(const float *gy, const float *y, const float *
 }
 
 // The engine's one-launch small-map conv + BatchNorm (k_conv_bn_dir, dip_dir.h) on its own: the same
-// launch dipnet_forward makes for a conv with BN on a map of <= dir_max_p() pixels.
+// launch dipnet_forward makes for a conv with BN on a map of <= kDirMaxP pixels.
 extern "C" int lrs_conv_bn_small_f32(const float *x, int Cin, int H, int W, const float *w, const float *bias, int Cout,
                                      int k, int stride, int pad, int pad_mode, int upsample, const float *gamma,
                                      const float *beta, int lip, int act, float *z, float *y, float *mean, float *invstd,
@@ -1225,8 +1161,6 @@ struct lrs_dipnet {
         bool sm = false;              // small map: forward / data gradient on k_conv_sm (dip_sm.h)
         bool upc = false;             // upsampled 3 x 3: forward / data gradient by output parity class
         bool sm_dgrad = false;        // ... data gradient through the adjoint table below
-        bool fork_pt = true;          // weight-gradient side stream: fork after its BN backward (else its
-                                      // weight gradient waits for the next fork point)
         int64_t adj_off = -1;         // the lists in the workspace (shorts, sm_adj_dim)
         std::vector<int> adj;         // host copy (sm_adj_table), uploaded at bind
         int64_t wtab_off = -1;        // small map: the weight gradient's gather table (sm_wgrad_table)
@@ -1242,20 +1176,10 @@ struct lrs_dipnet {
     // chain and the preparation of every conv but the first, whose planes the main stream writes from
     // the raw weights (prep_head table); its BatchNorm kernel divides by the scale (sn_overlap)
     bool sn_overlap = false;
-    int n_prep_side = 0;
     int64_t prep_head_off_bytes = 0, prep_side_off_bytes = 0;
-    // prep_split: the data-gradient planes (read first in the backward) prepared on the side stream beside
-    // the forward; the forward planes and W / scale stay where they were (prep_f: forward / prep_fs: the
-    // overlapped side table, without the data-gradient planes; prep_d: the data-gradient planes only)
-    bool prep_split = false, wd_pending = false;
-    int n_prep_d = 0;
-    int64_t prep_f_off_bytes = 0, prep_fs_off_bytes = 0, prep_d_off_bytes = 0;
-    hipEvent_t ev_wdgo = nullptr, ev_wd = nullptr;
-    hipEvent_t ev_head = nullptr, ev_sigma = nullptr;
-    // split_ev: ev_sigma right after the Lanczos (the first BatchNorm needs the scale only) and ev_prep
-    // after the other convs' planes (the second conv waits for it); else ev_sigma after both
-    hipEvent_t ev_prep = nullptr;
-    bool split_ev = false;
+    // ev_sigma right after the Lanczos (the first BatchNorm needs the scale only) and ev_prep after the
+    // other convs' planes (the second conv waits for it)
+    hipEvent_t ev_head = nullptr, ev_sigma = nullptr, ev_prep = nullptr;
     int64_t headcnt_off_bytes = 0;   // per-channel counters of k_mse_head (zeroed at bind, reset by the kernel)
     bool head_fusable = false;       // last node = conv without BN: loss + its activation backward in one kernel
     // ... and when that conv is a 1x1 on k_pw, the loss head runs in the conv's own epilogue (PwHead);
@@ -1272,17 +1196,15 @@ struct lrs_dipnet {
     hipGraphExec_t gexec = nullptr;
     hipGraph_t graph = nullptr;
     // weight gradients run on a side stream beside the data-gradient chain (fork per conv node
-    // after its BN backward, join before Adam)
+    // after its BN backward, join before Adam) at every size: beside the concurrent sparse-coding kernel
+    // the second stream keeps the DIP its share of the chip (configs[2] 4.73 -> 5.19 outer it/s,
+    // round 1); at 36^2 it was slower in round 1 (1.03 -> 1.19 ms per step) and is faster since the
+    // small-map fork points pair up (round 4, interleaved: 0.729 -> 0.676 ms per step)
     hipStream_t side = nullptr;   // the one for the current call's priority (one of sides)
     std::vector<std::pair<int, hipStream_t>> sides;   // (priority, stream): one per priority seen
     std::vector<hipEvent_t> ev_fork;
     hipEvent_t ev_join = nullptr;
-    int64_t part2_off = 0;
-    int64_t part3_off = -1;   // grouped backward (group_bwd): the main stream's weight-gradient partials
-    bool group_bwd = false;   // a conv's data and weight gradients in one launch (k_gemm_s3x2; tuning build)
-    // forking pays only when the layers fill the chip (measured: 512^2 skip net 13.0 -> 12.1 ms
-    // per step; 196^2 even; 36^2 7-16 % slower from the event overhead)
-    bool fork_w = false;
+    int64_t part2_off = 0;   // the side stream's split-K partials
     struct Key {
         const void *x, *t, *m, *es, *ring;
         float lr, b1, b2, eps;
@@ -1297,9 +1219,6 @@ struct lrs_dipnet {
     ConvPrep *prep() const { return (ConvPrep *)(ws + prep_off_bytes); }
     ConvPrep *prep_head() const { return (ConvPrep *)(ws + prep_head_off_bytes); }
     ConvPrep *prep_side() const { return (ConvPrep *)(ws + prep_side_off_bytes); }
-    ConvPrep *prep_f() const { return (ConvPrep *)(ws + prep_f_off_bytes); }
-    ConvPrep *prep_fs() const { return (ConvPrep *)(ws + prep_fs_off_bytes); }
-    ConvPrep *prep_d() const { return (ConvPrep *)(ws + prep_d_off_bytes); }
     int *headcnt() const { return (int *)(ws + headcnt_off_bytes); }
     double *loss_acc() const { return (double *)(ws + misc_off_bytes); }
     int *step() const { return (int *)(ws + misc_off_bytes + 8); }
@@ -1323,20 +1242,19 @@ bool bn_bwd_fusable(const lrs_dipnet *net, int j) {
     return N.d.kind == LRS_NODE_CONV && N.d.bn && N.P <= 4 * kBn1Threads && bn_split(N.P) == 1;
 }
 
-// workgroups per conv of the per-step weight preparation (LRS_DIP_PREP_WG overrides: tuning only)
-inline int prep_blocks() {
-    static const int v = (int)std::max<int64_t>(1, tune_knob("LRS_DIP_PREP_WG", 512));
-    return v;
-}
+// workgroups per conv of the per-step weight preparation
+constexpr int kPrepWg = 512;
+
+// the largest map (output pixels) whose last 1x1 conv takes the loss head into its epilogue (PwHead): only
+// on small maps, 36^2 step 0.578 -> 0.571 ms, but 196^2 1.187 -> 1.192 ms (3 interleaved rounds,
+// profiles/r06/ab/fused_head.txt): there the epilogue's extra 60 MB (target in, gz out) lengthens the
+// 481-workgroup conv by more than the separate k_mse_head launch costs
+constexpr int64_t kHeadPwMaxP = 4096;
 
 // the largest small map (output pixels) whose conv + BatchNorm run as one k_conv_bn_dir launch:
 // the 9^2 and smaller maps (36^2 step 0.635 -> 0.621 ms; 196^2 within noise; with the 13^2 / 18^2
-// maps too both are slower: 196^2 +28 us, 36^2 +3 us; tuning build, 2 interleaved rounds,
-// profiles/r05/dir/)
-inline int64_t dir_max_p() {
-    static const int64_t v = tune_knob("LRS_DIP_DIR_P", 100);
-    return v;
-}
+// maps too both are slower: 196^2 +28 us, 36^2 +3 us; 2 interleaved rounds, profiles/r05/dir/)
+constexpr int64_t kDirMaxP = 100;
 
 // raw_first (dipnet_step's overlapped sigma, lrs_dipnet::sn_overlap): the spectral-norm chain and
 // the weight preparation were enqueued by the caller (the first conv's planes from the raw weights on
@@ -1351,21 +1269,11 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
         if (rc) return rc;
     }
     if (net->n_prep && !raw_first) {   // W / scale and the bf16 planes of every conv, one launch
-        const bool split = net->prep_split && step_begin && net->side && net->ev_wdgo && net->ev_wd;
-        hipLaunchKernelGGL(k_conv_prep, dim3(prep_blocks(), net->n_prep), dim3(256), 0, st, split ? net->prep_f() : net->prep(),
-                           net->f(net->scale_off), step_begin ? net->loss_acc() : nullptr, net->step());
-        if (split && net->n_prep_d) {   // the data-gradient planes beside the forward (the backward waits)
-            hipError_t e = hipEventRecord(net->ev_wdgo, st);
-            if (e == hipSuccess) e = hipStreamWaitEvent(net->side, net->ev_wdgo, 0);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k_conv_prep, dim3(prep_blocks(), net->n_prep_d), dim3(256), 0, net->side, net->prep_d(),
-                               net->f(net->scale_off), (double *)nullptr, net->step());
-            if ((e = hipEventRecord(net->ev_wd, net->side)) != hipSuccess) return (int)e;
-            net->wd_pending = true;
-        }
+        hipLaunchKernelGGL(k_conv_prep, dim3(kPrepWg, net->n_prep), dim3(256), 0, st, net->prep(), net->f(net->scale_off),
+                           step_begin ? net->loss_acc() : nullptr, net->step());
         LRS_CHECK_LAUNCH();
     }
-    bool prep_waited = !(raw_first && net->split_ev);
+    bool prep_waited = !raw_first;
     for (size_t i = 0; i < net->nodes.size(); ++i) {
         auto &N = net->nodes[i];
         float *out = net->f(N.out_off);
@@ -1387,7 +1295,7 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
             // a 1x1 conv without BN applies its activation in the pointwise kernel's epilogue
             const bool act_in_pw = !bn && plain_unit(N.g) && wp;
             DirGeom dg;
-            if (bn && N.sm && !N.upc && !(raw_first && i == 0) && N.P <= dir_max_p() && dir_geom(N.g, dg)) {
+            if (bn && N.sm && !N.upc && !(raw_first && i == 0) && N.P <= kDirMaxP && dir_geom(N.g, dg)) {
                 // one launch: direct fp32 conv + BatchNorm (+act), one workgroup per output channel
                 const BnArgs a{z, out, net->params + N.gm_off, net->params + N.bt_off, net->f(N.mean_off),
                                net->f(N.istd_off), net->bnstats + N.rs_off, net->bnstats + N.rs_off + N.C, nullptr, N.C,
@@ -1441,12 +1349,8 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
                                net->f(N.istd_off), net->bnstats + N.rs_off, net->bnstats + N.rs_off + N.C, nullptr, N.C,
                                (int)N.P, 1, (int)N.P, 1, N.d.act, 1e-5f, 0.1f, lip, 1};
                 const float *pp = nsplit > 1 ? (const float *)net->f(net->part_off) : nullptr;
-                if (bnr_small_wg() && nq == 3 && N.P <= 4 * 256 * 10)
-                    hipLaunchKernelGGL((k_bn_fwd_r<10, 256>), dim3(1, N.C), dim3(256), 0, st, pp, nsplit,
-                                       (const float *)(net->params + N.b_off), a, sdiv);
-                else
-                    LRS_BNR_SWITCH(nq, k_bn_fwd_r, dim3(1, N.C), dim3(kBn1Threads), 0, st, pp, nsplit,
-                                   (const float *)(net->params + N.b_off), a, sdiv);
+                LRS_BNR_SWITCH(nq, k_bn_fwd_r, dim3(1, N.C), dim3(kBn1Threads), 0, st, pp, nsplit,
+                               (const float *)(net->params + N.b_off), a, sdiv);
                 rc = LRS_OK;
             } else if (fuse && nsplit > 1) {
                 const BnArgs a{z, out, net->params + N.gm_off, net->params + N.bt_off, net->f(N.mean_off),
@@ -1523,19 +1427,14 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
     // (the workspace's 16-B alignment completes the conditions lrs_dipnet_create checked: every
     // buffer offset is a multiple of 256 B, so the first conv's BatchNorm kernel then takes the
     // register / fused form the overlap needs, and the forward cannot refuse it mid-step)
-    const bool overlap = net->sn_overlap && net->side && net->ev_head && net->ev_sigma && (!net->split_ev || net->ev_prep) &&
-                         al16(net->ws);
+    const bool overlap = net->sn_overlap && net->side && net->ev_head && net->ev_sigma && net->ev_prep && al16(net->ws);
     if (overlap) {
         // the spectral-norm Grams here (alone they take 19 us at 196^2; on the side stream beside the
         // first conv, 50), then the rest of the chain (Gram reduce, Lanczos) and the preparation of every
         // conv but the first on the side stream beside the first conv, whose planes come from the raw
         // weights here
         // (the Gram reduce too: on the side stream beside the first conv it took 23 us instead of 6)
-        // the first conv's planes on 8 grid rows of kSnSplit workgroups (one row: the kernel took 36.7 us,
-        // its 16 plane workgroups the longest; 8 rows: 19.2 us, 196^2 step 1.194 -> 1.177 ms, 3 interleaved
-        // rounds, profiles/r06/ab/head_plane_rows.txt; LRS_DIP_HEAD_PLANE_ROWS, tuning only)
-        static const int prow = (int)std::max<int64_t>(1, std::min<int64_t>(64, tune_knob("LRS_DIP_HEAD_PLANE_ROWS", 8)));
-        hipLaunchKernelGGL(k_sn_gram_head, dim3(kSnSplit, net->n_sn + prow), dim3(256), 0, st, net->table(), net->gram(),
+        hipLaunchKernelGGL(k_sn_gram_head, dim3(kSnSplit, net->n_sn + kHeadPlaneRows), dim3(256), 0, st, net->table(), net->gram(),
                            net->n_sn, (const ConvPrep *)net->prep_head(), net->loss_acc(), net->step());
         hipLaunchKernelGGL(k_sn_gram_reduce, dim3(kSnPairs, net->n_sn), dim3(256), 0, st, net->table(), net->gram());
         hipError_t e = hipEventRecord(net->ev_head, st);
@@ -1543,20 +1442,14 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL(k_sn_sigma, dim3(net->n_sn), dim3(256), 0, net->side, net->table(), net->gram(),
                            net->f(net->sigma_off), net->f(net->scale_off), net->ln_lambda, (long long *)nullptr);
-        if (net->split_ev && (e = hipEventRecord(net->ev_sigma, net->side)) != hipSuccess) return (int)e;
-        const bool split = net->prep_split && net->ev_wd;
-        if (net->n_prep_side)
-            hipLaunchKernelGGL(k_conv_prep, dim3(prep_blocks(), net->n_prep_side), dim3(256), 0, net->side,
-                               split ? net->prep_fs() : net->prep_side(), net->f(net->scale_off), (double *)nullptr,
-                               net->step());
-        e = hipEventRecord(net->split_ev ? net->ev_prep : net->ev_sigma, net->side);
-        if (e != hipSuccess) return (int)e;
-        if (split && net->n_prep_d) {   // the data-gradient planes after the forward's (the backward waits)
-            hipLaunchKernelGGL(k_conv_prep, dim3(prep_blocks(), net->n_prep_d), dim3(256), 0, net->side, net->prep_d(),
+        // the first BatchNorm waits for the scale only, the second conv for the planes as well: 196^2 step
+        // 1.185 -> 1.179 ms against one event after both (3 interleaved rounds,
+        // profiles/r06/ab/split_event_and_es.txt)
+        if ((e = hipEventRecord(net->ev_sigma, net->side)) != hipSuccess) return (int)e;
+        if (net->n_prep)
+            hipLaunchKernelGGL(k_conv_prep, dim3(kPrepWg, net->n_prep), dim3(256), 0, net->side, net->prep_side(),
                                net->f(net->scale_off), (double *)nullptr, net->step());
-            if ((e = hipEventRecord(net->ev_wd, net->side)) != hipSuccess) return (int)e;
-            net->wd_pending = true;
-        }
+        if ((e = hipEventRecord(net->ev_prep, net->side)) != hipSuccess) return (int)e;
         LRS_CHECK_LAUNCH();
     }
     const int n = (int)net->nodes.size();
@@ -1581,19 +1474,12 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
     // the input conv's weight-gradient split-K sum is finished inside Adam (one launch less on the
     // step's tail)
     AdamPend pw{};
-    // (LRS_DIP_ES_SIDE=0, tuning only: the ES update after Adam on this stream, as until round 6)
-    static const bool es_side = tune_knob("LRS_DIP_ES_SIDE", 1) != 0;
     const EsJob esj{out, (int64_t)Lst.C * Lst.P, ring, es};
-    const bool es_beside = es && es_side && net->fork_w;
-    rc = dipnet_backward(net, x, st, net->head_fusable, &pw, fused_head, es_beside ? &esj : nullptr);
+    rc = dipnet_backward(net, x, st, net->head_fusable, &pw, fused_head, es ? &esj : nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL(k_adam, dim3(ew_blocks((net->n_params + 3) / 4, 8192)), dim3(kEw), 0, st, net->params,
                        (const float *)net->grads, net->am, net->av, net->n_params, (const int *)net->step(), lr, b1, b2,
                        eps, pw);
-    if (es && !es_beside) {
-        rc = es_update(out, (int64_t)Lst.C * Lst.P, ring, es, st);
-        if (rc) return rc;
-    }
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
@@ -1602,16 +1488,13 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
 // gradient into net->grads (the input gets none: the reference's DIP input needs no gradient).
 // Weight gradient of conv node i on stream ws: reads dL/dz, the layer input and the scale only.
 // scratch: its split-K partials (part2 on the side stream; part on the main one)
-// split-K workgroup target of the weight gradients on the side stream (LRS_DIP_WGRAD_SPLIT_WG, tuning
-// only): fewer splits write fewer partials and hold fewer CUs beside the data-gradient chain
-inline int wgrad_split_target() {
-    static const int v = (int)std::max<int64_t>(1, std::min<int64_t>(512, tune_knob("LRS_DIP_WGRAD_SPLIT_WG", 512)));
-    return v;
-}
+// split-K workgroup target of the weight gradients on the side stream: fewer splits would write fewer
+// partials and hold fewer CUs beside the data-gradient chain (at most the 512 the workspace is sized for)
+constexpr int kWgradSplitWg = 512;
 
 int weight_grad(lrs_dipnet *net, int i, const float *x, hipStream_t ws, float *scratch, int *wsplit_out = nullptr) {
     if (wsplit_out) *wsplit_out = 1;
-    const int wt = ws == net->side ? wgrad_split_target() : 512;
+    const int wt = ws == net->side ? kWgradSplitWg : 512;
     auto &N = net->nodes[i];
     const int t = N.d.in0;
     const float *gz = net->f(N.gz_off);
@@ -1638,99 +1521,6 @@ int weight_grad(lrs_dipnet *net, int i, const float *x, hipStream_t ws, float *s
                     N.col_off < 0, nullptr, wsplit_out, wt);
 }
 
-// Is conv node i a fork point of the weight-gradient side stream (Node::fork_pt, lrs_dipnet_create)?
-// LRS_DIP_FORK_SET (tuning only) = the node indices that fork instead, e.g. "13,12,11,10,7,4,1,0".
-bool fork_at(const lrs_dipnet *net, int i) {
-    static const char *set = tune_str("LRS_DIP_FORK_SET");
-    if (!set) return net->nodes[i].fork_pt;
-    for (const char *p = set; *p;) {
-        char *e = nullptr;
-        const long v = strtol(p, &e, 10);
-        if (e == p) break;
-        if (v == i) return true;
-        p = (*e == ',' || *e == '.') ? e + 1 : e;   // '.' too (tools/gpu.sh specs split on ',')
-    }
-    return false;
-}
-
-// A conv's data gradient and weight gradient as ONE launch (k_gemm_s3x2: the data-gradient tiles
-// first, then the weight-gradient tiles; both read dL/dz), then the fold of the data gradient and the
-// weight gradient's split-K sum, all on stream st: no side-stream fork for this conv.  The stride-1
-// implicit convs (LdDgradTM over the padded domain) and the parity-class upsampled ones.  Returns
-// LRS_E_UNSUPPORTED for a conv it does not take (the caller keeps the two-stream path).
-// Tuning build only (LRS_DIP_GROUP=1): parity-green, but the 196^2 step takes 1.259 ms against 1.189
-// with the side stream (profiles/r06/ab/grouped_backward.txt): the weight gradients'
-// overlap with the folds and BatchNorm kernels is worth more than the forks it saves.
-#ifdef LRS_TUNING
-int group_bwd_conv(lrs_dipnet *net, int i, const float *x, float *gx, int accum_gx, hipStream_t st) {
-    auto &N = net->nodes[i];
-    const ConvGeom &g = N.g;
-    if (N.sm || N.col_off >= 0 || plain_unit(g) || N.wpre_off < 0 || !gx) return LRS_E_UNSUPPORTED;
-    const float *gz = net->f(N.gz_off), *xin = net->tensor(N.d.in0, x);
-    const bool sn = N.sn_index >= 0;
-    const float *wdiv = sn ? net->f(net->scale_off) + N.sn_index : nullptr;
-    float *gw = net->grads + N.w_off, *part = net->f(net->part_off), *part3 = net->f(net->part3_off);
-    float *dcol = net->f(net->dcol_off);
-    const int64_t cap = net->part_cap;
-    const int P = (int)N.P, Cout = N.C, Cop = r16(Cout);
-    if (N.upc) {
-        const int K1 = 16 * Cop, Qe = (g.Hs + 2) * (g.Ws + 2), Q = g.Hs * g.Ws, N2 = 4 * g.Cin;
-        const Split s1 = choose_split(g.Cin, Qe, K1, LRS_DIP_SPLIT_BF16, true, dgrad_split_target());
-        const Split s2 = choose_split(Cout, 4 * N2, Q, LRS_DIP_SPLIT_BF16, true);
-        if ((s1.S > 1 && cap < (int64_t)s1.S * g.Cin * Qe) || cap < (int64_t)s2.S * 4 * Cout * N2) return LRS_E_WORKSPACE;
-        const GemmArgs a1{nullptr, nullptr, s1.S > 1 ? part : dcol, nullptr, nullptr, g.Cin, Qe, K1, s1.kchunk, 0};
-        const GemmArgs a2{nullptr, nullptr, part3, nullptr, nullptr, Cout, N2, Q, s2.kchunk, 0, 4, g.Ws, 0, 0};
-        const S3Grid d1{(unsigned)((Qe + 127) / 128), (unsigned)((g.Cin + 127) / 128), (unsigned)s1.S};
-        const S3Grid d2{(unsigned)((N2 + 127) / 128), (unsigned)((Cout + 127) / 128), (unsigned)(4 * s2.S)};
-        const unsigned nwg = ((d1.x * d1.y * d1.z + 7) & ~7u) + d2.x * d2.y * d2.z;
-        const __bf16 *wd = (const __bf16 *)net->f(N.wpre_off) + wprep_fwd_elems(g, Cout, true);
-        hipLaunchKernelGGL((k_gemm_s3x2<LdPre, LdUpDgradTM, LdGzCls, LdWgradCls>), dim3(nwg), dim3(kGemmThreads), 0, st, a1,
-                           LdPre{wd, (int64_t)g.Cin * K1, K1, g.Cin}, LdUpDgradTM{gz, Cout * g.Ho * g.Wo * 4, g, Cout, Cop, nullptr},
-                           d1, a2, LdGzCls{gz, g.Hs, g.Ws, g.Wo, Cout, 0}, LdWgradCls{xin, g.Cin * Q * 4, g, nullptr, 0, 0}, d2);
-        ConvGeom fg = g;
-        fg.up = 0; fg.Hu = g.Hs; fg.Wu = g.Ws; fg.pad = 1; fg.pad_mode = kPadClamp;
-        hipLaunchKernelGGL(k_fold_pad, dim3((unsigned)((Q + 255) / 256), (unsigned)std::min(g.Cin, 65535)), dim3(256), 0, st,
-                           s1.S > 1 ? part : dcol, s1.S, (int64_t)g.Cin * Qe, fg, gx, accum_gx);
-        const int64_t n = (int64_t)Cout * g.Cin * 9;
-        hipLaunchKernelGGL(k_upc_wgrad_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)part3, s2.S,
-                           Cout, g.Cin, wdiv, gw);
-        LRS_CHECK_LAUNCH();
-        return LRS_OK;
-    }
-    const int kk = g.k * g.k, Qp = (g.Hu + 2 * g.pad) * (g.Wu + 2 * g.pad), Kc = (int)N.Kc;
-    if (g.stride != 1 || up_eff_k(g) || (int64_t)g.Cin * Qp > (int64_t)Kc * P || !conv_implicit_ok(g, Cout))
-        return LRS_E_UNSUPPORTED;
-    const Split s1 = choose_split(g.Cin, Qp, kk * Cop, LRS_DIP_SPLIT_BF16, true, dgrad_split_target());
-    const Split s2 = choose_split(Cout, Kc, P, LRS_DIP_SPLIT_BF16, true);
-    if ((s1.S > 1 && cap < (int64_t)s1.S * g.Cin * Qp) || (s2.S > 1 && cap < (int64_t)s2.S * Cout * Kc))
-        return LRS_E_WORKSPACE;
-    const GemmArgs a1{nullptr, nullptr, s1.S > 1 ? part : dcol, nullptr, nullptr, g.Cin, Qp, kk * Cop, s1.kchunk, 0};
-    const GemmArgs a2{nullptr, nullptr, s2.S > 1 ? part3 : gw, nullptr, wdiv, Cout, Kc, P, s2.kchunk, 0};
-    const S3Grid d1{(unsigned)((Qp + 127) / 128), (unsigned)((g.Cin + 127) / 128), (unsigned)s1.S};
-    const S3Grid d2{(unsigned)((Kc + 127) / 128), (unsigned)((Cout + 127) / 128), (unsigned)s2.S};
-    const unsigned nwg = ((d1.x * d1.y * d1.z + 7) & ~7u) + d2.x * d2.y * d2.z;
-    const __bf16 *wd = (const __bf16 *)net->f(N.wpre_off) + wprep_fwd_elems(g, Cout);
-    hipLaunchKernelGGL((k_gemm_s3x2<LdPre, LdDgradTM, LdDense<true>, LdWgradTM>), dim3(nwg), dim3(kGemmThreads), 0, st, a1,
-                       LdPre{wd, (int64_t)g.Cin * kk * Cop, kk * Cop, g.Cin}, LdDgradTM{gz, Cout * P * 4, g, Cout, Cop, nullptr},
-                       d1, a2, LdDense<true>{gz, P, Cout}, LdWgradTM{xin, g.Cin * g.Hs * g.Ws * 4, g, nullptr, 0}, d2);
-    if (s1.S == 1 && !g.up && g.Ws % 4 == 0 && g.Cin <= 65535 && al16(gx)) {
-        const int q = g.Hs * (g.Ws / 4);
-        hipLaunchKernelGGL(k_fold_pad1q, dim3((unsigned)((q + 255) / 256), (unsigned)g.Cin), dim3(256), 0, st, (const float *)dcol,
-                           g, gx, accum_gx);
-    } else {
-        hipLaunchKernelGGL(k_fold_pad, dim3((unsigned)((g.Hs * g.Ws + 255) / 256), (unsigned)std::min(g.Cin, 65535)), dim3(256), 0,
-                           st, (const float *)(s1.S > 1 ? part : dcol), s1.S, (int64_t)g.Cin * Qp, g, gx, accum_gx);
-    }
-    if (s2.S > 1) {
-        const int64_t MN = (int64_t)Cout * Kc;
-        hipLaunchKernelGGL(k_gemm_reduce, dim3((unsigned)((MN + kEw - 1) / kEw)), dim3(kEw), 0, st, (const float *)part3, s2.S,
-                           Cout, Kc, (const float *)nullptr, wdiv, 0, gw);
-    }
-    LRS_CHECK_LAUNCH();
-    return LRS_OK;
-}
-#endif
-
 // pw (lrs_dipnet_train_steps): the input conv's weight gradient may leave its split-K partials for
 // k_adam to finish (AdamPend; pw->part == nullptr when nothing is pending)
 int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_done, AdamPend *pw, bool head_reduce,
@@ -1746,7 +1536,7 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
         return r;
     };
     // the fused loss head's sums (PwHead): the bias gradient of the last conv (read by Adam only) and the
-    // loss, on the side stream with the first weight gradients (or here, without a side stream)
+    // loss, on the side stream with the first weight gradient (or here, where none forks)
     auto head_sums = [&](hipStream_t hs) {
         if (!head_reduce) return;
         const auto &Lh = net->nodes[n - 1];
@@ -1755,31 +1545,23 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
         hipLaunchKernelGGL(k_head_loss, dim3(1), dim3(64), 0, hs, (const double *)net->closs(), Lh.C, net->loss_acc());
         head_reduce = false;
     };
-    if (!net->fork_w) head_sums(st);
-    if (net->wd_pending) {   // the data-gradient planes prepared on the side stream (prep_split)
-        const hipError_t e = hipStreamWaitEvent(st, net->ev_wd, 0);
-        if (e != hipSuccess) return (int)e;
-        net->wd_pending = false;
-    }
     // gradient buffers: the first contribution to a tensor writes, later ones accumulate
     std::vector<char> written(n + 1, 0);
     written[n] = 1;
-    // weight gradients queued for the side stream, launched after the fork that follows node j's BN
-    // backward (every queued node's dL/dz is complete by then)
-    std::vector<int> wq;
     int first_conv = 0;
     while (first_conv < n && net->nodes[first_conv].d.kind != LRS_NODE_CONV) ++first_conv;
-    auto flush_w = [&](int j) -> int {
-        if (wq.empty()) return LRS_OK;
+    // conv node j's weight gradient on the side stream, forked right after its BN backward (its dL/dz is
+    // complete by then).  Until round 5 a run of small maps forked every second conv (a fork cost the
+    // critical stream ~7 us with system-scope events); with the device-scope events (ensure_side) forking
+    // at every conv is faster at both sizes: 196^2 1.192 -> 1.189 ms, 36^2 0.584 -> 0.580 ms (3 interleaved
+    // rounds, profiles/r06/ab/fork_sets.txt).
+    auto fork_w = [&](int j) -> int {
         hipError_t e = hipEventRecord(net->ev_fork[j], st);
         if (e == hipSuccess) e = hipStreamWaitEvent(net->side, net->ev_fork[j], 0);
         if (e != hipSuccess) return (int)e;
         head_sums(net->side);
         if (const int r = es_side(net->side)) return r;
-        for (int q : wq)
-            if (const int r = weight_grad(net, q, x, net->side, net->f(net->part2_off))) return r;
-        wq.clear();
-        return LRS_OK;
+        return weight_grad(net, j, x, net->side, net->f(net->part2_off));
     };
     // a small-map data gradient may leave dL/dy of the next node as split-K partials, finished by
     // that node's k_reduce_bn_bwd1 (pend = the partials, pend_S their count)
@@ -1817,32 +1599,15 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
             const float *w = sn ? net->f(N.wn_off) : net->params + N.w_off;
             float *gx = t > 0 ? net->f(net->nodes[t - 1].grad_off) : nullptr;
             const float *wdiv = sn ? net->f(net->scale_off) + N.sn_index : nullptr;
-#ifdef LRS_TUNING
-            // grouped (tuning build): data and weight gradient in one launch on this stream
-            if (net->group_bwd && gx) {
-                rc = group_bwd_conv(net, i, x, gx, written[t], st);
-                if (rc == LRS_OK) {
-                    written[t] = 1;
-                    continue;
-                }
-                if (rc != LRS_E_UNSUPPORTED) return rc;
-            }
-#endif
-            // weight gradient on the side stream (reads gz, the layer input and the scale only); the
-            // nodes between two fork points queue theirs until the next one (fork_at)
-            if (net->fork_w && !(t == 0 && i == first_conv)) {
-                wq.push_back(i);
-                if (fork_at(net, i) && (rc = flush_w(i))) return rc;
+            // weight gradient on the side stream (reads gz, the layer input and the scale only)
+            if (!(t == 0 && i == first_conv)) {
+                if ((rc = fork_w(i))) return rc;
             } else {
-                // no fork: or the first conv on the input, after which the main stream has no work left
-                // of its own (a fork there only adds the event latency to the step's tail); it uses the
-                // main stream's scratch, free by then, beside whatever the side stream still runs
-                if (net->fork_w && (rc = flush_w(i))) return rc;
+                // the first conv on the input, after which the main stream has no work left of its own (a
+                // fork there only adds the event latency to the step's tail); it uses the main stream's
+                // scratch, free by then, beside whatever the side stream still runs
                 int wsplit = 1;
-                // (LRS_DIP_DEFER_EXPLICIT=0, tuning only: the explicit (small-map) input conv's sum by
-                // k_gemm_reduce instead, as before round 6)
-                static const bool defer_explicit = tune_knob("LRS_DIP_DEFER_EXPLICIT", 1) != 0;
-                const bool defer = pw && t == 0 && i == first_conv && (defer_explicit || N.col_off < 0);
+                const bool defer = pw != nullptr;
                 if ((rc = weight_grad(net, i, x, st, net->f(net->part_off), defer ? &wsplit : nullptr))) return rc;
                 if (defer && wsplit > 1)
                     *pw = AdamPend{net->f(net->part_off), wsplit, N.w_off, (int64_t)N.C * N.Kc,
@@ -1922,8 +1687,7 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
             if (tb > 0) written[tb] = 1;
         }
     }
-    if (net->fork_w) {   // join the side stream before anyone reads the weight gradients
-        if ((rc = flush_w(0))) return rc;
+    {   // join the side stream before anyone reads the weight gradients
         hipError_t e = hipEventRecord(net->ev_join, net->side);
         if (e == hipSuccess) e = hipStreamWaitEvent(st, net->ev_join, 0);
         if (e != hipSuccess) return (int)e;
@@ -1958,12 +1722,6 @@ extern "C" int lrs_dipnet_create(const lrs_dip_node *nodes, int n_nodes, int C, 
     auto fail = [&](int rc) { delete net; return rc; };
     net->opts = o;
     net->implicit = o.precision == LRS_DIP_SPLIT_BF16;
-    // weight gradients on a side stream at every size: beside the concurrent sparse-coding kernel
-    // the second stream keeps the DIP its share of the chip (configs[2] 4.73 -> 5.19 outer it/s,
-    // round 1); at 36^2 it was slower in round 1 (1.03 -> 1.19 ms per step) and is faster since the
-    // small-map fork points pair up (round 4, interleaved: 0.729 -> 0.676 ms per step)
-    net->fork_w = true;
-    net->fork_w = tune_knob("LRS_DIP_FORK", net->fork_w ? 1 : 0) != 0;   // tuning build only
     int64_t pofs = 0, rofs = 0, ofs = 0, max_dz = 0, max_dcol = 0, part = 0, max_bnpart = 0;
     int n_sn = 0;
     for (int i = 0; i < n_nodes; ++i) {
@@ -1991,23 +1749,23 @@ extern "C" int lrs_dipnet_create(const lrs_dip_node *nodes, int n_nodes, int C, 
                 N.wn_off = ofs; ofs += align64(N.C * N.Kc);
                 if (N.C * N.Kc > net->max_w) net->max_w = N.C * N.Kc;
             }
-            if (plain_unit(N.g) && net->implicit && pw_ok(N.g, N.C) && N.P >= implicit_min_pixels() &&
+            if (plain_unit(N.g) && net->implicit && pw_ok(N.g, N.C) && N.P >= kImplicitMinP &&
                 wprep_elems(N.g, N.C) < INT32_MAX / 3) {
                 N.wpre_off = ofs;   // 1x1 on k_pw: its pre-split weight planes
                 ofs += align64((wprep_elems(N.g, N.C) + 1) / 2);
             }
             if (!plain_unit(N.g)) {
-                if (!(net->implicit && conv_implicit_ok(N.g, N.C) && N.P >= implicit_min_pixels())) {
+                if (!(net->implicit && conv_implicit_ok(N.g, N.C) && N.P >= kImplicitMinP)) {
                     // col: the weight gradient's explicit im2col (written in the backward for a
                     // small-map conv, whose forward gathers it inside k_conv_sm)
                     N.col_off = ofs;
                     ofs += align64(N.Kc * N.P);
-                    if (net->implicit && sm_enabled() && N.d.k <= 3 && conv_implicit_ok(N.g, N.C) &&
+                    if (net->implicit && N.d.k <= 3 && conv_implicit_ok(N.g, N.C) &&
                         wprep_elems(N.g, N.C) < INT32_MAX / 3) {
                         N.sm = true;
                         N.wpre_off = ofs;
                         ofs += align64((wprep_elems(N.g, N.C) + 1) / 2);
-                        if (N.P <= kSmWgradOneLaunchP && net->fork_w) {
+                        if (N.P <= kSmWgradOneLaunchP) {
                             N.wtab = sm_wgrad_table(N.g);
                             N.wtab_off = ofs;
                             ofs += align64((int64_t)N.wtab.size());
@@ -2078,12 +1836,6 @@ extern "C" int lrs_dipnet_create(const lrs_dip_node *nodes, int n_nodes, int C, 
         N.grad_off = ofs; ofs += align64((int64_t)N.C * N.P);
         net->nodes.push_back(N);
     }
-    // Fork points: every conv forks its weight gradient to the side stream right after its BatchNorm
-    // backward (Node::fork_pt stays true).  Until round 5 a run of small maps forked every second conv
-    // (a fork cost the critical stream ~7 us with system-scope events); with the device-scope events
-    // (ensure_side) forking at every conv is faster at both sizes: 196^2 1.192 -> 1.189 ms, 36^2 0.584
-    // -> 0.580 ms (3 interleaved rounds, profiles/r06/ab/fork_sets.txt).  LRS_DIP_FORK_SET (tuning
-    // build) still picks the fork points for A/B.
     net->n_sn = n_sn;
     net->n_params = pofs;
     net->n_bnstats = rofs;
@@ -2091,10 +1843,6 @@ extern "C" int lrs_dipnet_create(const lrs_dip_node *nodes, int n_nodes, int C, 
     net->dcol_off = ofs; ofs += align64(max_dcol);
     net->part_off = ofs; ofs += align64(part);
     net->part2_off = ofs; ofs += align64(part);
-#ifdef LRS_TUNING
-    net->group_bwd = tune_knob("LRS_DIP_GROUP", 0) != 0;
-#endif
-    if (net->group_bwd) { net->part3_off = ofs; ofs += align64(part); }
     net->part_cap = part;
     net->sigma_off = ofs; ofs += align64(n_sn > 0 ? n_sn : 1);
     net->scale_off = ofs; ofs += align64(n_sn > 0 ? n_sn : 1);
@@ -2111,54 +1859,33 @@ extern "C" int lrs_dipnet_create(const lrs_dip_node *nodes, int n_nodes, int C, 
     bytes += (size_t)round_up((int64_t)((net->n_prep > 0 ? net->n_prep : 1) * sizeof(ConvPrep)), 256);
     // sigma beside the first conv: a spectrally normalised first conv on the network input whose
     // BatchNorm kernel finishes its split-K sum (k_bn_fwd_r or k_reduce_bn1, at least 2 partials), read
-    // from weight planes; only where the weight gradients already fork (the side stream exists)
+    // from weight planes
     {
         const auto &N0 = net->nodes[0];
-        bool ok = net->fork_w && n_sn > 0 && N0.d.kind == LRS_NODE_CONV && N0.d.in0 == 0 && N0.sn_index >= 0 &&
+        bool ok = n_sn > 0 && N0.d.kind == LRS_NODE_CONV && N0.d.in0 == 0 && N0.sn_index >= 0 &&
                   N0.d.bn && N0.wpre_off >= 0 && !plain_unit(N0.g) && !N0.upc;
         if (ok) {
             const bool fuse = N0.P <= 4 * kBn1Threads && bn_split(N0.P) == 1;
             const bool nq = bn_reg_q(N0.P, N0.P % 4 == 0) > 0;
             const int kk = N0.g.k * N0.g.k, K = kk * r16(N0.g.Cin);
             const int S = N0.sm ? sm_split(N0.C, (int)N0.P, K).S
-                                : choose_split(N0.C, (int)N0.P, K, LRS_DIP_SPLIT_BF16, true, fwd_split_target()).S;
+                                : choose_split(N0.C, (int)N0.P, K, LRS_DIP_SPLIT_BF16, true, kFwdSplitWg).S;
             // only where the first conv is long enough to hide the side chain (~70 us at 196^2: the Gram
             // reduce, Lanczos and the other convs' planes); at 36^2 the 18^2 first conv takes 7 us and the
-            // overlap measured slower (tuning build: 0.647 -> 0.663 ms per step)
-            ok = (fuse || nq) && S >= 2 && N0.P >= tune_knob("LRS_DIP_SN_OVERLAP_MINP", kForkBigP);
+            // overlap measured slower (0.647 -> 0.663 ms per step)
+            ok = (fuse || nq) && S >= 2 && N0.P >= kForkBigP;
         }
-        net->sn_overlap = ok && tune_knob("LRS_DIP_SN_OVERLAP", 1) != 0;
-        // the first BatchNorm waits for the scale only, the second conv for the planes as well: 196^2 step
-        // 1.185 -> 1.179 ms (3 interleaved rounds, profiles/r06/ab/split_event_and_es.txt)
-        net->split_ev = net->sn_overlap && tune_knob("LRS_DIP_SPLIT_EV", 1) != 0;
+        net->sn_overlap = ok;
     }
-    net->n_prep_side = net->n_prep;
     net->prep_head_off_bytes = (int64_t)bytes;
     bytes += 256;   // one ConvPrep
     net->prep_side_off_bytes = (int64_t)bytes;
     bytes += (size_t)round_up((int64_t)((net->n_prep > 0 ? net->n_prep : 1) * sizeof(ConvPrep)), 256);
-    {
-        const int64_t tb = round_up((int64_t)((net->n_prep > 0 ? net->n_prep : 1) * sizeof(ConvPrep)), 256);
-        net->prep_f_off_bytes = (int64_t)bytes;
-        bytes += (size_t)tb;
-        net->prep_fs_off_bytes = (int64_t)bytes;
-        bytes += (size_t)tb;
-        net->prep_d_off_bytes = (int64_t)bytes;
-        bytes += (size_t)tb;
-        // off: 196^2 1.189 -> 1.192 ms, 36^2 0.572 -> 0.576 ms with it (3 interleaved rounds,
-        // profiles/r06/ab/prep_split_dropped.txt): the extra event and launch cost more than the half of
-        // the preparation it takes off the critical stream (LRS_DIP_PREP_SPLIT=1, tuning only)
-        net->prep_split = net->fork_w && net->n_prep > 0 && tune_knob("LRS_DIP_PREP_SPLIT", 0) != 0;
-    }
     net->head_fusable = net->nodes.back().d.kind == LRS_NODE_CONV && net->nodes.back().d.bn == 0 &&
                         net->nodes.back().C <= 65535;
     {
         const auto &Lh = net->nodes.back();
-        // only on small maps: 36^2 step 0.578 -> 0.571 ms, but 196^2 1.187 -> 1.192 ms (3 interleaved rounds,
-        // profiles/r06/ab/fused_head.txt): there the epilogue's extra 60 MB (target in, gz out) lengthens
-        // the 481-workgroup conv by more than the separate k_mse_head launch costs
-        net->head_pw = net->head_fusable && plain_unit(Lh.g) && Lh.wpre_off >= 0 && tune_knob("LRS_DIP_HEAD_PW", 1) != 0 &&
-                       Lh.P <= tune_knob("LRS_DIP_HEAD_PW_MAXP", 4096);
+        net->head_pw = net->head_fusable && plain_unit(Lh.g) && Lh.wpre_off >= 0 && Lh.P <= kHeadPwMaxP;
         if (net->head_pw) {
             net->hpart_off_bytes = (int64_t)bytes;   // [2][C][<= ceil(P / 64) workgroups]
             bytes += (size_t)round_up(2 * (int64_t)Lh.C * ((Lh.P + 63) / 64) * 8, 256);
@@ -2186,8 +1913,6 @@ extern "C" void lrs_dipnet_destroy(lrs_dipnet *net) {
     if (net->ev_head) (void)hipEventDestroy(net->ev_head);
     if (net->ev_sigma) (void)hipEventDestroy(net->ev_sigma);
     if (net->ev_prep) (void)hipEventDestroy(net->ev_prep);
-    if (net->ev_wdgo) (void)hipEventDestroy(net->ev_wdgo);
-    if (net->ev_wd) (void)hipEventDestroy(net->ev_wd);
     for (auto &ps : net->sides) (void)hipStreamDestroy(ps.second);
     delete net;
 }
@@ -2270,26 +1995,6 @@ extern "C" int lrs_dipnet_bind(lrs_dipnet *net, float *params, float *grads, flo
         if (e == hipSuccess) e = hipMemcpy(net->prep_head(), &head, sizeof(ConvPrep), hipMemcpyHostToDevice);
         if (e == hipSuccess)
             e = hipMemcpy(net->prep_side(), side.data(), sizeof(ConvPrep) * side.size(), hipMemcpyHostToDevice);
-    }
-    if (net->prep_split && !prep.empty()) {
-        std::vector<ConvPrep> pf(prep), pd;
-        for (auto &c : pf) c.wd = nullptr;
-        for (const auto &c : prep)
-            if (c.wd) {
-                ConvPrep d = c;
-                d.Wn = nullptr;
-                d.wf = nullptr;
-                pd.push_back(d);
-            }
-        net->n_prep_d = (int)pd.size();
-        if (e == hipSuccess) e = hipMemcpy(net->prep_f(), pf.data(), sizeof(ConvPrep) * pf.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !pd.empty())
-            e = hipMemcpy(net->prep_d(), pd.data(), sizeof(ConvPrep) * pd.size(), hipMemcpyHostToDevice);
-        if (net->sn_overlap) {
-            std::vector<ConvPrep> fs(pf);
-            fs[0].wf = nullptr;   // (the first conv's forward planes: the head slot, raw weights)
-            if (e == hipSuccess) e = hipMemcpy(net->prep_fs(), fs.data(), sizeof(ConvPrep) * fs.size(), hipMemcpyHostToDevice);
-        }
     }
     if (e == hipSuccess) e = hipMemset(net->misc_off_bytes + net->ws, 0, 256);
     if (e == hipSuccess) e = hipMemset(net->headcnt(), 0, sizeof(int) * (net->nodes.back().C + 1));
@@ -2389,7 +2094,6 @@ extern "C" const float *lrs_dipnet_node_buffer(const lrs_dipnet *net, int node, 
 // on a stream of another priority only selects a different one: no host synchronisation and no
 // graph drop (a captured graph holds its own nodes, not the stream).
 static int ensure_side(lrs_dipnet *net, hipStream_t st) {
-    if (!net->fork_w) return LRS_OK;
     int prio = 0;
     hipError_t e = hipStreamGetPriority(st, &prio);
     if (e != hipSuccess) return (int)e;
@@ -2399,36 +2103,19 @@ static int ensure_side(lrs_dipnet *net, hipStream_t st) {
             return LRS_OK;
         }
     hipStream_t s = nullptr;
-#ifdef LRS_TUNING
-    // A/B only: the side stream on a subset of the CUs (every k-th CU left to the critical stream)
-    static const int cuskip = (int)tune_knob("LRS_DIP_SIDE_CUSKIP", 0);
-    if (cuskip > 1) {
-        int dev = 0, ncu = 0;
-        if ((e = hipGetDevice(&dev)) == hipSuccess)
-            e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return (int)e;
-        std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-        for (int i = 0; i < ncu; ++i)
-            if (i % cuskip != cuskip - 1) mask[(size_t)i / 32] |= 1u << (i % 32);
-        e = hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data());
-    } else
-#endif
-        e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio);
+    e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio);
     if (e != hipSuccess) return (int)e;
     net->sides.emplace_back(prio, s);
     net->side = s;
     // The fork / join events only order kernels of this device against each other (nothing on the host
     // waits on them), so they are recorded with device-scope fences -- what a kernel boundary inside one
     // stream has -- instead of the default system-scope release, whose cache write-back the critical
-    // stream paid at every fork (tools/micro/fork_cost: DESIGN.md §5).  LRS_DIP_SYSFENCE=1 (tuning
-    // build only) keeps the default events for A/B.
-    static const unsigned evf = hipEventDisableTiming | (tune_knob("LRS_DIP_SYSFENCE", 0) ? 0u : hipEventDisableSystemFence);
+    // stream paid at every fork (tools/micro/fork_cost: DESIGN.md §5).
+    constexpr unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
     if (!net->ev_join) e = hipEventCreateWithFlags(&net->ev_join, evf);
     if (e == hipSuccess && !net->ev_head) e = hipEventCreateWithFlags(&net->ev_head, evf);
     if (e == hipSuccess && !net->ev_sigma) e = hipEventCreateWithFlags(&net->ev_sigma, evf);
     if (e == hipSuccess && !net->ev_prep) e = hipEventCreateWithFlags(&net->ev_prep, evf);
-    if (e == hipSuccess && !net->ev_wdgo) e = hipEventCreateWithFlags(&net->ev_wdgo, evf);
-    if (e == hipSuccess && !net->ev_wd) e = hipEventCreateWithFlags(&net->ev_wd, evf);
     for (size_t i = 0; i < net->ev_fork.size() && e == hipSuccess; ++i)
         if (!net->ev_fork[i]) e = hipEventCreateWithFlags(&net->ev_fork[i], evf);
     return (int)e;

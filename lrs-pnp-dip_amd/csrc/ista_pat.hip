@@ -332,17 +332,6 @@ size_t ista_pat_workspace(int64_t n, int64_t K, int64_t npat) {
 
 // Waves per workgroup: 8 for K > 128 (configs[2] sparse coding alone: 2.00 ms vs 2.10 ms with 4;
 // profiles/r04/ista_pat/), 4 below (one or two atom tiles per wave).
-#ifdef LRS_TUNING
-static int pat_waves_knob() {
-    const char *e = getenv("LRS_ISTA_PAT_WAVES");
-    return e ? atoi(e) : 0;
-}
-static int pat_wpe_knob() {   // LRS_ISTA_PAT_WPE=4: the 128-register form (two workgroups per CU)
-    const char *e = getenv("LRS_ISTA_PAT_WPE");
-    return e ? atoi(e) : 0;
-}
-#endif
-
 template <int NQ, int S, int WPE = 2>
 static int launch_pat_k(const IstaPatParams &p, int64_t max_wg, hipStream_t st) {
     static std::atomic<uint64_t> opted{0};   // per device
@@ -394,23 +383,17 @@ int ista_pat_launch(const float *Yb, const uint8_t *obs_pat, int64_t npat, const
     if (ntiles == 0) return LRS_OK;
     IstaPatParams p{Yb, obs_pat, plan, DAf, DTf, QAf, alpha, thr, coefs, phi, x0, (int)n_pad, (int)K, Nit, prox,
                     nb, ntiles, npat, 7.0};
-    int waves = NQ >= 16 ? 8 : 4;
-#ifdef LRS_TUNING
-    if (const int kw = pat_waves_knob()) waves = kw;
-#endif
+    const int waves = NQ >= 16 ? 8 : 4;
     switch (NQ) {
     case 4: return launch_pat_k<4, 4>(p, max_wg, st);
     case 8: return launch_pat_k<8, 4>(p, max_wg, st);
     case 16:
         // 8 waves, registers unbounded (192, one workgroup per CU).  The 128-register bound (two
-        // workgroups per CU; LRS_ISTA_PAT_WPE=4, tuning build) is bit-identical and a little faster
+        // workgroups per CU; WPE = 4) is bit-identical and a little faster
         // (configs[3]'s sparse coding 11.3 -> 10.6 ms, configs[2]'s beside the DIP 1.745 -> 1.683 ms;
         // the configs[2] bench 7.87 either way, profiles/r04/ista_pat_wpe/), but spills 37 registers
         // (152 B of scratch per lane, 29 with a 2-deep ring): the PMC pass then measured 1.26 GB of
         // fabric traffic per configs[2] launch instead of 122 MB (profiles/r04/ista_pat_spill/).
-#ifdef LRS_TUNING
-        if (waves == 8 && pat_wpe_knob() == 4) return launch_pat_k<16, 8, 4>(p, max_wg, st);
-#endif
         return waves == 8 ? launch_pat_k<16, 8>(p, max_wg, st) : launch_pat_k<16, 4>(p, max_wg, st);
     default: return launch_pat_k<32, 8>(p, max_wg, st);
     }

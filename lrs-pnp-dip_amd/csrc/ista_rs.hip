@@ -390,12 +390,7 @@ static int launch_rs_k(const IstaRsParams &p, int64_t max_wg, hipStream_t st) {
     if (max_wg > 0 && tiles > max_wg) tiles = max_wg;
     static std::atomic<uint64_t> opted{0};   // dynamic LDS beyond 64 KiB, per device
     if (const int rc = lds_opt_in((const void *)k_ista_rs<NQ, MINW, S>, 160 * 1024, opted)) return rc;
-    size_t lds = rs_lds_bytes(NQ, S);
-#ifdef LRS_TUNING
-    // A/B only: LRS_ISTA_RS_LDS = dynamic LDS per workgroup (bytes, >= the kernel's), e.g. 98304 holds
-    // the sparse coding to one workgroup per CU beside the DIP
-    if (const char *e = getenv("LRS_ISTA_RS_LDS")) lds = std::max<size_t>(lds, (size_t)atoll(e));
-#endif
+    const size_t lds = rs_lds_bytes(NQ, S);
     hipLaunchKernelGGL((k_ista_rs<NQ, MINW, S>), dim3((unsigned)tiles), dim3(64 * S), lds, st, p);
     LRS_CHECK_LAUNCH();
     return LRS_OK;

@@ -29,7 +29,8 @@ def test_library_exports_header_symbols():
 def test_no_process_wide_mode():
     """reentrant, no global mutable state.  Every mode is a per-call option
     (lrs_ista_opts, lrs_dip_opts) or fixed per handle; the only setter takes a lrs_dipnet; the
-    product library reads no environment variable (A/B knobs exist only in the tuning build)."""
+    library reads no environment variable (a variant for A/B is a second build, selected by the
+    caller: lrspnp/_lib.py's LRSPNP_LIB)."""
     src = open(os.path.join(REPO, "include", "lrspnp.h")).read()
     setters = re.findall(r"int\s+(lrs_[a-z0-9_]*set_[a-z0-9_]*)\s*\(([^)]*)\)", src)
     assert setters, "expected the per-handle lrs_dipnet_set_ln_lambda"
@@ -44,6 +45,8 @@ def test_no_process_wide_mode():
     nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
     und = subprocess.run([nm, "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     assert not re.search(r"\bgetenv\b", und), "the product library must not read the environment"
+    dip = open(os.path.join(REPO, "lrs-pnp-dip_amd", "csrc", "dipnet.hip")).read()
+    assert not re.search(r"\bgetenv\b", dip), "the DIP engine's constants are compile-time, not environment knobs"
 
 
 def test_block_grid_matches_oracle():

@@ -5,8 +5,9 @@
 #                                      literal 200^2 skip net, configs[1], native 36^2 (synthetic and the
 #                                      reference's image), ES-on lines, torchrun N = 1)
 #   tools/gpu.sh steptime SPEC...      DIP step-time A/B: SPEC = label[:ENV=V[,ENV=V...]][@args],
-#                                      interleaved over $ROUNDS rounds (default 2); ENV LRSPNP_LIB=tune
-#                                      selects the tuning build; args go to tools/dip_steptime.py
+#                                      interleaved over $ROUNDS rounds (default 2); ENV LRSPNP_LIB=<v>
+#                                      (or an absolute path) selects a variant build of the library;
+#                                      args go to tools/dip_steptime.py
 #   tools/gpu.sh host SPEC...          host enqueue vs GPU time per step (tools/host_enqueue.py)
 #   tools/gpu.sh trace NAME CMD...     rocprofv3 kernel trace + stats of CMD into profiles-ready files
 #   tools/gpu.sh pmc NAME CMD...       the HBM counter passes (FETCH_SIZE, WRITE_SIZE) of CMD
@@ -19,7 +20,6 @@ set -o pipefail
 export TMPDIR=/tmp
 O=${OUT:-gpurun_out/run}
 mkdir -p $O
-T=$PWD/lrs-pnp-dip_amd/lrspnp/liblrspnp_hip_tune.so
 what=$1
 shift
 
@@ -34,7 +34,7 @@ run_spec() {   # $1 = tool, $2 = spec
   IFS=',' read -ra kv <<< "$envs"
   for e in "${kv[@]}"; do
     [[ -z $e ]] && continue
-    # LRSPNP_LIB=<v>: the build lrs-pnp-dip_amd/lrspnp/liblrspnp_hip_<v>.so (tune = the tuning build)
+    # LRSPNP_LIB=<v>: the build lrs-pnp-dip_amd/lrspnp/liblrspnp_hip_<v>.so
     [[ $e == LRSPNP_LIB=* && $e != LRSPNP_LIB=/* ]] && e="LRSPNP_LIB=$PWD/lrs-pnp-dip_amd/lrspnp/liblrspnp_hip_${e#LRSPNP_LIB=}.so"
     ev+=("$e")
   done
