@@ -224,13 +224,20 @@ typedef struct {
  *     and back-transformation phases spread over many workgroups (bit-identical result); for a
  *     caller whose eigensolver is on the critical path (a row-slab shard), not beside a
  *     chip-filling sparse-coding kernel.
- * s_out (nullable, device, B doubles) receives the singular values (descending).  B <= 256: up to
- * 198 bands the eigensolver holds the packed fp64 Gram in its CU's LDS, above it (the 224-band
- * cubes) the same one-workgroup chain works on the packed Gram in ws (L2-resident);
- * LRS_E_UNSUPPORTED above 256 (main_LRS_PnP.py:112-124's np.linalg.svd takes any B). */
+ * s_out (nullable, device, B doubles) receives the singular values (descending).  Up to 198 bands
+ * the eigensolver holds the packed fp64 Gram in its CU's LDS, above it (the 224-band cubes) the
+ * same one-workgroup chain works on the packed Gram in ws (L2-resident), up to 256 bands.
+ * Wide cubes, 256 < B <= lrs_svt_max_bands() = 512: the Gram and U = Z (I - E) are tiled over
+ * column panels, and the eigen stage is always the one-workgroup Jacobi chain, whatever the
+ * LRS_SVT_JACOBI bit says (the state word reports path 3).  LRS_SVT_WARM alone enables its warm
+ * start there: _gram then forms the warm-start products V^T (G V).  LRS_SVT_MULTI_WG with
+ * B > 256 is LRS_E_UNSUPPORTED, as is any B above 512 (main_LRS_PnP.py:112-124's np.linalg.svd
+ * takes any B).  The workspace grows with the rotation log: 131 MB at (P, B) = (40000, 512). */
 #define LRS_SVT_WARM 1
 #define LRS_SVT_JACOBI 2
 #define LRS_SVT_MULTI_WG 4
+/* The largest band count the SVT calls accept (host-only): 512. */
+int64_t lrs_svt_max_bands(void);
 size_t lrs_svt_workspace(int64_t P, int64_t B);
 int lrs_svt_f32(const float *X, const float *L2, float c2, int64_t P, int64_t B, double tau,
                 float *U, double *s_out, int warm, void *ws, size_t ws_bytes, void *stream);
@@ -247,7 +254,8 @@ int lrs_svt_finish_f32(const float *X, const float *L2, float c2, int64_t P, int
  * unfolded cube per rank sums the slabs' Grams in place (all-reduce of Bp*Bp doubles) between
  * _gram and _finish: the Gram is additive over pixel rows (single cube on
  * several GPUs). Not valid with LRS_SVT_JACOBI | LRS_SVT_WARM (its warm-start products are
- * formed from the local Gram inside _gram). Host-only, no device access. */
+ * formed from the local Gram inside _gram), nor for the wide cubes above 256 bands, whose eigen
+ * stage is that path: LRS_E_UNSUPPORTED there. Host-only, no device access. */
 int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, int64_t *ld);
 
 /* ---- col2im + closed-form X update + dual updates ------------------------------------------

@@ -13,12 +13,15 @@
 //      Z V diag((s-tau)_+/s) V^T == U_s (S-tau)_+ V_h, and E is small so its f32 rounding costs
 //      << 1e-6 relative in U.
 // The whole chain runs on its own stream beside the sparse-coding kernel.
+// Wide cubes (256 < B <= 512, svt_wide.h): 1 and 5 are tiled over column panels, and 2-4 run on the
+// packed triangle in the workspace whatever solver the caller asked for.
 #include <math.h>
 
 #include <algorithm>
 #include <utility>
 
 #include "lrs_common.h"
+#include "svt_wide.h"
 
 namespace lrs {
 
@@ -30,7 +33,9 @@ constexpr int kJacobiThreads = 1024;
 // flags (at Bp = 200 the chain would need 164,128 B > 160 KiB): up to kLdsMaxBp the one-workgroup
 // chain keeps it in LDS; above (the 224-band cubes of BASELINE configs[3]/[4]) the same chain runs
 // on the packed triangle in the workspace (L2-resident: 224^2/2 x 8 B = 200 KB), with full
-// workgroup barriers instead of LDS-only ones.  kMaxBp: every phase's register / lane layout.
+// workgroup barriers instead of LDS-only ones.  kMaxBp: every phase's register / lane layout;
+// above it, up to kWideMaxBp (svt_wide.h), the wide-band path: tiled Gram and apply kernels around
+// the Jacobi chain on the workspace triangle (1 MB at Bp = 512).
 constexpr int kLdsMaxBp = 198;
 constexpr int kMaxBp = 256;
 constexpr int kMaxSweeps = 40;
@@ -40,17 +45,17 @@ __host__ __device__ constexpr int gram_nt(int64_t B) { return B <= 208 ? 13 : 16
 __host__ __device__ constexpr int gram_npairs(int nt) { return nt * (nt + 1) / 2; }
 
 struct SvtWs {
-    double *partial;  // [kGramSlabs][16x16 tile pairs][256]  Gram partials
+    double *partial;  // [kGramSlabs, wide kWideSlabs][16x16 tile pairs][256]  Gram partials
     double *G;        // [Bp][Bp]
     double *A0;       // [Bp][Bp]  V^T G V (warm start)
     double *T;        // [Bp][Bp]  scratch
     double *V[2];     // [Bp][Bp]  eigenvectors, double-buffered
     double *lam;      // [Bp]      eigenvalues (diag of the converged A)
-    double *rot;      // [kMaxSweeps*(Bp-1)][Bp/2][2]  (c, s) per round and pair
+    double *rot;      // [kMaxSweeps*(Bp-1)][Bp/2][2]  (c, s) per round and pair (84 MB at Bp = 512)
     double *beta;     // [Bp]      Householder scalars (tridiagonal path)
-    double *F;        // [Bp][4][Bp] pivoted LU rows of T - lambda_i I (inverse iteration)
+    double *F;        // [Bp][4][Bp] pivoted LU rows of T - lambda_i I (inverse iteration; none when wide)
     float *E;         // [B][B]
-    float *Fp;        // [ap_steps(B)][B][4]  I - E in the apply kernel's fragment order
+    float *Fp;        // [ap_steps(B), wide wide_ap_steps(B)][B][4]  I - E in the apply kernels' fragment order
     int *state;       // [0] V valid, [1] current V buffer, [2] rounds, [3] sweeps,
                       // [4] path of the last solve (1 tridiagonal, 2 Jacobi fallback, 3 Jacobi)
     int64_t Bp;
@@ -67,8 +72,11 @@ static SvtWs svt_ws_layout(void *base, int64_t P, int64_t B) {
         return r;
     };
     const size_t mat = (size_t)w.Bp * w.Bp * sizeof(double);
+    const bool wide = w.Bp > kMaxBp;   // tiles of every 16 columns, fewer slabs; no tridiagonal solver
+    const size_t tiles = wide ? (size_t)kWideSlabs * gram_npairs((int)((B + 15) / 16))
+                              : (size_t)kGramSlabs * gram_npairs(gram_nt(B));
     w.state = (int *)take(256);
-    w.partial = (double *)take((size_t)kGramSlabs * gram_npairs(gram_nt(B)) * 256 * sizeof(double));
+    w.partial = (double *)take(tiles * 256 * sizeof(double));
     w.G = (double *)take(mat);
     w.A0 = (double *)take(mat);
     w.T = (double *)take(mat);
@@ -77,8 +85,8 @@ static SvtWs svt_ws_layout(void *base, int64_t P, int64_t B) {
     w.lam = (double *)take((size_t)w.Bp * sizeof(double));
     w.rot = (double *)take((size_t)kMaxSweeps * (w.Bp - 1) * (w.Bp / 2) * 2 * sizeof(double));
     w.beta = (double *)take((size_t)w.Bp * sizeof(double));
-    w.F = (double *)take((size_t)4 * mat);
-    w.Fp = (float *)take((size_t)ap_steps(B) * B * 4 * sizeof(float));
+    w.F = (double *)take(wide ? 0 : (size_t)4 * mat);
+    w.Fp = (float *)take((size_t)(wide ? wide_ap_steps(B) : ap_steps(B)) * B * 4 * sizeof(float));
     w.E = (float *)take((size_t)B * B * sizeof(float));
     return w;
 }
@@ -398,8 +406,11 @@ constexpr int kVRows = 64;
 constexpr int kLogRounds = 16;
 
 // Rows i0 .. i0 + vrows - 1 of Vn = Vo J_1 ... J_R (Vo = identity when null); 1024 threads.
-// vrows = kVRows, or half that where 64 rows of Bp > kLdsMaxBp exceed the LDS (vrebuild_rows).
-__host__ __device__ constexpr int vrebuild_rows(int Bp) { return Bp <= kLdsMaxBp ? kVRows : kVRows / 2; }
+// vrows = kVRows, half that where 64 rows of Bp > kLdsMaxBp exceed the LDS, a quarter above kMaxBp
+// (at Bp = 512: 16 rows 65,536 B + the staged log 81,920 B = 147,456 B of the 160 KiB).
+__host__ __device__ constexpr int vrebuild_rows(int Bp) {
+    return Bp <= kLdsMaxBp ? kVRows : Bp <= kMaxBp ? kVRows / 2 : kVRows / 4;
+}
 __host__ __device__ constexpr size_t vrebuild_lds(int Bp) {
     return sizeof(double) * ((size_t)vrebuild_rows(Bp) * Bp + (size_t)kLogRounds * (Bp / 2) * 2) +
            sizeof(short) * (size_t)kLogRounds * (Bp / 2) * 2;
@@ -811,6 +822,16 @@ extern "C" size_t lrs_svt_workspace(int64_t P, int64_t B) {
     return svt_ws_bytes(P, B);
 }
 
+extern "C" int64_t lrs_svt_max_bands(void) { return kWideMaxBp; }
+
+// Above kMaxBp the wide-band path serves, up to kWideMaxBp; it has no multi-workgroup solver.
+static int svt_shape_check(int64_t B, int warm) {
+    const int64_t Bp = B + (B & 1);
+    if (Bp > kWideMaxBp) return LRS_E_UNSUPPORTED;
+    if (Bp > kMaxBp && (warm & LRS_SVT_MULTI_WG)) return LRS_E_UNSUPPORTED;
+    return LRS_OK;
+}
+
 extern "C" int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, int64_t *ld) {
     if (P <= 0 || B <= 0 || !offset_bytes || !ld) return LRS_E_INVALID;
     if (B + (B & 1) > kMaxBp) return LRS_E_UNSUPPORTED;
@@ -824,7 +845,7 @@ extern "C" int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, 
 extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64_t P, int64_t B, int warm, void *ws,
                                 size_t ws_bytes, void *stream) {
     if (!X || !ws || P <= 0 || B <= 0) return LRS_E_INVALID;
-    if (B + (B & 1) > kMaxBp) return LRS_E_UNSUPPORTED;
+    if (svt_shape_check(B, warm) != LRS_OK) return LRS_E_UNSUPPORTED;
     if (ws_bytes < svt_ws_bytes(P, B)) return LRS_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     SvtWs w = svt_ws_layout(ws, P, B);
@@ -833,10 +854,16 @@ extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64
         if (e != hipSuccess) return (int)e;
     }
     const int Bp = (int)w.Bp;
-    int64_t rows = ((P + kGramSlabs - 1) / kGramSlabs + 3) / 4 * 4;
+    const bool wide = Bp > kMaxBp;
+    const int slabs = wide ? kWideSlabs : kGramSlabs;
+    int64_t rows = ((P + slabs - 1) / slabs + 3) / 4 * 4;
     const int nslab = (int)((P + rows - 1) / rows);
-    const int nt = gram_nt(B);
-    if (nt == 13)
+    const int nt = wide ? (int)((B + 15) / 16) : gram_nt(B);
+    if (wide) {
+        const int npan = wide_npanels((int)B);
+        hipLaunchKernelGGL(k_gram_wide, dim3((unsigned)nslab, (unsigned)(npan * (npan + 1) / 2)), dim3(256), 0, st, X,
+                           L2, c2, P, (int)B, rows, nt, w.partial);
+    } else if (nt == 13)
         hipLaunchKernelGGL((k_gram_mfma<13, 4>), dim3((unsigned)nslab), dim3(256), 0, st, X, L2, c2, P, (int)B, rows,
                            w.partial);
     else
@@ -846,7 +873,7 @@ extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64
     hipLaunchKernelGGL(k_gram_reduce16, dim3((unsigned)((Bp * Bp + 255) / 256)), dim3(256), 0, st, w.partial, nslab,
                        nt, (int)B, Bp, w.G);
     LRS_CHECK_LAUNCH();
-    if ((warm & LRS_SVT_WARM) && (warm & LRS_SVT_JACOBI)) {
+    if ((warm & LRS_SVT_WARM) && ((warm & LRS_SVT_JACOBI) || wide)) {
         // A0 = V^T (G V) with the current V (unused when V is not valid yet: Jacobi starts from G)
         const dim3 g16((Bp + 15) / 16, (Bp + 15) / 16);
         hipLaunchKernelGGL(k_gemm_f64_state, g16, dim3(256), 0, st, w, 0);
@@ -857,22 +884,40 @@ extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64
     return LRS_OK;
 }
 
+// U = Z (I - E) from the F = I - E the eigen stage left in w.Fp: the apply kernel of this band count
+static int svt_apply(const float *X, const float *L2, float c2, int64_t P, int64_t B, const SvtWs &w, float *U,
+                     hipStream_t st) {
+    const dim3 agrid((unsigned)((P + 64 * kApRows - 1) / (64 * kApRows)));
+    if (w.Bp > kMaxBp)
+        hipLaunchKernelGGL((k_svt_apply_wide<kWideApRows, kWideApTiles>),
+                           dim3((unsigned)((P + 64 * kWideApRows - 1) / (64 * kWideApRows)),
+                                (unsigned)((B + 16 * kWideApTiles - 1) / (16 * kWideApTiles))),
+                           dim3(256), 0, st, X, L2, c2, w.Fp, P, (int)B, U);
+    else if (B <= 200)
+        hipLaunchKernelGGL((k_svt_apply_f<kApRows, 13, 50>), agrid, dim3(256), 0, st, X, L2, c2, w.Fp, P, (int)B, U);
+    else
+        hipLaunchKernelGGL((k_svt_apply_f<kApRows, 16, 64>), agrid, dim3(256), 0, st, X, L2, c2, w.Fp, P, (int)B, U);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
 // Stage 2: one-workgroup Jacobi (runs beside the sparse-coding kernel), V replay, E, U.
 extern "C" int lrs_svt_finish_f32(const float *X, const float *L2, float c2, int64_t P, int64_t B, double tau,
                                   float *U, double *s_out, int warm, void *ws, size_t ws_bytes, void *stream) {
     if (!X || !U || !ws || P <= 0 || B <= 0 || tau < 0.0) return LRS_E_INVALID;
-    if (B + (B & 1) > kMaxBp) return LRS_E_UNSUPPORTED;
+    if (svt_shape_check(B, warm) != LRS_OK) return LRS_E_UNSUPPORTED;
     if (ws_bytes < svt_ws_bytes(P, B)) return LRS_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     SvtWs w = svt_ws_layout(ws, P, B);
     const int Bp = (int)w.Bp;
     const bool ga = Bp > kLdsMaxBp;   // the packed triangle in the workspace, not in LDS
+    const bool wide = Bp > kMaxBp;    // the Jacobi chain whatever the flag word asks for
     const int nb = eig_nb(Bp);
     // LDS of the Jacobi solve: the packed triangle (unless ga) + its rotation tables
     const size_t jaux = sizeof(double) * ((size_t)Bp + 16) + sizeof(int) * (2 * Bp);
     const size_t smem = (ga ? 0 : sizeof(double) * (size_t)Bp * (Bp + 1) / 2) + jaux;
     const size_t vsmem = vrebuild_lds(Bp);
-    if (warm & LRS_SVT_JACOBI) {
+    if (wide || (warm & LRS_SVT_JACOBI)) {
         const int jwarm = warm & LRS_SVT_WARM;
         // dynamic LDS above 64 KiB must be opted into; request exactly what this shape needs
         const void *kj = ga ? (const void *)k_jacobi_lds<true> : (const void *)k_jacobi_lds<false>;
@@ -934,13 +979,7 @@ extern "C" int lrs_svt_finish_f32(const float *X, const float *L2, float c2, int
         hipLaunchKernelGGL(k_sorted_singular_values, dim3(1), dim3(256), 0, st, w, (int)B, s_out);
         LRS_CHECK_LAUNCH();
     }
-    const dim3 agrid((unsigned)((P + 64 * kApRows - 1) / (64 * kApRows)));
-    if (B <= 200)
-        hipLaunchKernelGGL((k_svt_apply_f<kApRows, 13, 50>), agrid, dim3(256), 0, st, X, L2, c2, w.Fp, P, (int)B, U);
-    else
-        hipLaunchKernelGGL((k_svt_apply_f<kApRows, 16, 64>), agrid, dim3(256), 0, st, X, L2, c2, w.Fp, P, (int)B, U);
-    LRS_CHECK_LAUNCH();
-    return LRS_OK;
+    return svt_apply(X, L2, c2, P, B, w, U, st);
 }
 
 extern "C" int lrs_svt_f32(const float *X, const float *L2, float c2, int64_t P, int64_t B, double tau, float *U,
@@ -988,11 +1027,15 @@ extern "C" int lrs_diag_svt_eig(void *ws, int64_t P, int64_t B, double *out, voi
     return e != hipSuccess ? (int)e : state[4];
 }
 
-// Diagnostics: the SVT apply alone (F = I - E from the last solve in ws).
+// Diagnostics: the SVT apply alone (F = I - E from the last solve in ws).  dbg 0: the kernel
+// lrs_svt_finish_f32 launches for this band count (tools/time_svt_wide.py); else row-tile variants.
 extern "C" int lrs_diag_svt_apply(const float *X, const float *L2, float c2, int64_t P, int64_t B, void *ws, float *U,
                                   int dbg, void *stream) {
+    if (!X || !U || !ws || P <= 0 || B <= 0) return LRS_E_INVALID;
+    if (svt_shape_check(B, 0) != LRS_OK) return LRS_E_UNSUPPORTED;
     SvtWs w = svt_ws_layout(ws, P, B);
     hipStream_t st = (hipStream_t)stream;
+    if (dbg == 0) return svt_apply(X, L2, c2, P, B, w, U, st);
     if (B > 200) return LRS_E_UNSUPPORTED;   // diagnostics of the B <= 200 apply variants only
     if (dbg == 1)
         hipLaunchKernelGGL(k_svt_apply_f<1>, dim3((unsigned)((P + 63) / 64)), dim3(256), 0, st, X, L2, c2, w.Fp, P,

@@ -1,0 +1,170 @@
+// SVT kernels of the wide-band path, 256 < B <= 512 (included by svt.hip, which holds the dispatch).
+// The one-workgroup kernels of B <= 256 keep every 16 x 16 tile pair of the Gram, and every column
+// of 16 rows of U, in one workgroup's registers; here both products are tiled over a 2-D grid so
+// that a workgroup's accumulators stay below those kernels' however wide the cube is.
+#pragma once
+
+#include "lrs_common.h"
+
+namespace lrs {
+
+constexpr int kWideMaxBp = 512;
+
+// ---- 1w. Gram G = Z^T Z on the fp64 matrix cores, row slab x column-panel pair ----------------
+// Panels of 64 columns (4 tiles of 16): workgroup (slab, pair (pa <= pb)) stages the slab's rows of
+// both panels kWideChunk at a time into LDS (Z = X + c2*L2 formed on the way, the float32 expression
+// of k_gram_mfma and the apply kernels), and wave w accumulates the 4 tiles (4 pa + w, 4 pb + b),
+// b = 0..3: 4 accumulators per wave.  Fragments as in k_gram_mfma: per k-step of 4 rows a lane
+// reads Z[r + (l>>4)][16 t + (l&15)].  Tiles (a <= b) go to partial[slab][pair index of (a, b) among
+// the nt (nt + 1) / 2 upper tile pairs][16*16], the layout k_gram_reduce16 sums in fixed order; the
+// tiles below the diagonal of a pair (pa, pa) and those past nt are computed and dropped.
+constexpr int kWideSlabs = 32;
+constexpr int kWidePanel = 64;
+constexpr int kWideChunk = 32;                    // rows per LDS chunk
+constexpr int kWideLd = 2 * kWidePanel + 16;      // row stride: lane groups 16 banks apart
+
+__host__ __device__ constexpr int wide_npanels(int B) { return (B + kWidePanel - 1) / kWidePanel; }
+
+__global__ __launch_bounds__(256) void k_gram_wide(const float *__restrict__ X, const float *__restrict__ L2,
+                                                   float c2, int64_t P, int B, int64_t rows_per_slab, int nt,
+                                                   double *__restrict__ partial) {
+    typedef double doublex4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) float Zs[kWideChunk * kWideLd];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, jl = lane & 15;
+    const int npan = wide_npanels(B);
+    int pa = 0, rem = blockIdx.y;
+    while (rem >= npan - pa) {
+        rem -= npan - pa;
+        ++pa;
+    }
+    const int pb = pa + rem;
+    const bool diag = pa == pb;
+    const int64_t pbeg = (int64_t)blockIdx.x * rows_per_slab, pend = min<int64_t>(P, pbeg + rows_per_slab);
+    // staging: thread -> LDS column cl (0..63 panel pa, 64..127 panel pb), rows (tid >> 7) + 2u
+    const int cl = tid & 127, hp = cl >> 6;
+    const int gc = kWidePanel * (hp ? pb : pa) + (cl & 63);
+    const bool cok = gc < B && !(hp && diag);
+    const int boff = diag ? 0 : kWidePanel;
+    doublex4 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[b] = doublex4{0.0, 0.0, 0.0, 0.0};
+    for (int64_t c0 = pbeg; c0 < pend; c0 += kWideChunk) {
+        const int rows = (int)min<int64_t>(kWideChunk, pend - c0);
+        float z[kWideChunk / 2];
+#pragma unroll
+        for (int u = 0; u < kWideChunk / 2; ++u) {
+            const int r = (tid >> 7) + 2 * u;
+            z[u] = 0.f;
+            if (cok && r < rows) {
+                const int64_t o = (c0 + r) * B + gc;
+                z[u] = X[o];
+                if (L2) z[u] = z[u] + c2 * L2[o];   // X + (1/mu_2)*lambda_2
+            }
+        }
+        __syncthreads();   // the previous chunk's fragments are read
+#pragma unroll
+        for (int u = 0; u < kWideChunk / 2; ++u) Zs[((tid >> 7) + 2 * u) * kWideLd + cl] = z[u];
+        __syncthreads();
+        const int rows4 = (rows + 3) & ~3;   // rows past `rows` are staged as zeros
+        for (int r = 0; r < rows4; r += 4) {
+            const float *zr = Zs + (r + g) * kWideLd + jl;
+            const double fa = (double)zr[16 * wv];
+            double fb[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) fb[b] = (double)zr[boff + 16 * b];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, fb[b], acc[b], 0, 0, 0);
+        }
+    }
+    // C/D layout of the f64 MFMA: column l & 15, row (l >> 4) + 4 i
+    const int npair = nt * (nt + 1) / 2;
+    double *out = partial + (int64_t)blockIdx.x * npair * 256;
+    const int a = 4 * pa + wv;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int tb = 4 * pb + b;
+        if (a < nt && tb < nt && a <= tb) {
+            const int pi = a * nt - ((a * (a - 1)) >> 1) + (tb - a);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) out[(int64_t)pi * 256 + (g + 4 * i) * 16 + jl] = acc[b][i];
+        }
+    }
+}
+
+// ---- 5w. U = Z (I - E) on the f32 matrix cores, row tile x column panel ------------------------
+// k_svt_apply_f with the columns split over blockIdx.y: a wave owns 16 RT rows and 16 NTL columns
+// (RT x NTL accumulator tiles) and walks K = B in ceil(B / 8) pairs of k-steps.  The k-step order
+// and F's fragment layout are k_svt_apply_f's (store_fp: Fp[(st * B + c) * 4 + g], a lane's two A
+// values of a pair are one float2 of its Z row), over 2 ceil(B / 8) k-steps.  Exact f32 products
+// (v_mfma_f32_16x16x4_f32), fp32 accumulation.  Rows >= P, columns >= B and k >= B are predicated:
+// nothing is read past a row's end, and rows k >= B of Fp (never written) are not read.
+__host__ __device__ constexpr int wide_ap_steps(int64_t B) { return 2 * (int)((B + 7) / 8); }
+constexpr int kWideApRows = 2;    // RT: 32 rows per wave, 128 per workgroup
+constexpr int kWideApTiles = 8;   // NTL: 128 columns per workgroup (16 accumulator tiles per wave)
+
+template <int RT, int NTL>
+__global__ __launch_bounds__(256) void k_svt_apply_wide(const float *__restrict__ X, const float *__restrict__ L2,
+                                                        float c2, const float *__restrict__ Fp, int64_t P, int B,
+                                                        float *__restrict__ U) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, jl = lane & 15;
+    const int64_t r0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (16 * RT);
+    if (r0 >= P) return;
+    const int c0 = blockIdx.y * (16 * NTL);
+    floatx4 acc[RT][NTL];
+#pragma unroll
+    for (int m = 0; m < RT; ++m)
+#pragma unroll
+        for (int t = 0; t < NTL; ++t) acc[m][t] = floatx4{0.f, 0.f, 0.f, 0.f};
+    const int nq = (B + 7) / 8;
+    for (int q = 0; q < nq; ++q) {
+        const int k = 8 * q + 2 * g;
+        float2 z[RT];
+#pragma unroll
+        for (int m = 0; m < RT; ++m) {
+            const int64_t row = r0 + 16 * m + jl;
+            z[m] = make_float2(0.f, 0.f);
+            if (row < P && k < B) {
+                if ((B & 1) == 0) {   // even B: 8-byte aligned rows, k + 1 < B
+                    z[m] = *reinterpret_cast<const float2 *>(&X[row * B + k]);
+                    if (L2) {
+                        const float2 l = *reinterpret_cast<const float2 *>(&L2[row * B + k]);
+                        z[m].x = z[m].x + c2 * l.x;   // X + (1/mu_2)*lambda_2
+                        z[m].y = z[m].y + c2 * l.y;
+                    }
+                } else {
+                    z[m].x = X[row * B + k];
+                    if (L2) z[m].x = z[m].x + c2 * L2[row * B + k];
+                    if (k + 1 < B) {
+                        z[m].y = X[row * B + k + 1];
+                        if (L2) z[m].y = z[m].y + c2 * L2[row * B + k + 1];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float *fb = Fp + (int64_t)(2 * q + h) * B * 4 + g;
+#pragma unroll
+            for (int t = 0; t < NTL; ++t) {
+                const int c = c0 + 16 * t + jl;
+                const float b = (c < B && k + h < B) ? fb[c * 4] : 0.0f;
+#pragma unroll
+                for (int m = 0; m < RT; ++m) acc[m][t] = mfma16x16x4(h ? z[m].y : z[m].x, b, acc[m][t]);
+            }
+        }
+    }
+    // acc[m][t][i] = U[r0 + 16m + 4g + i][c0 + 16t + jl]
+#pragma unroll
+    for (int m = 0; m < RT; ++m)
+#pragma unroll
+        for (int t = 0; t < NTL; ++t) {
+            const int c = c0 + 16 * t + jl;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int64_t r = r0 + 16 * m + 4 * g + i;
+                if (r < P && c < B) U[r * B + c] = acc[m][t][i];
+            }
+        }
+}
+
+}  // namespace lrs

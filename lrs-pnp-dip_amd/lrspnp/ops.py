@@ -14,7 +14,7 @@ from . import _lib as _libmod
 from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLAB, PROX_SOFT, LrsError, check,
                    device_lib, lib)
 
-__all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace",
+__all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
            "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
@@ -311,6 +311,11 @@ def nlm_matlab_col(g: torch.Tensor, h, out: torch.Tensor | None = None, stream=N
     return o.view_as(g)
 
 
+def svt_max_bands() -> int:
+    """The largest band count the SVT calls accept (lrs_svt_max_bands; host-only)."""
+    return int(lib().lrs_svt_max_bands())
+
+
 def svt_workspace(P: int, B: int, device) -> torch.Tensor:
     n = int(lib().lrs_svt_workspace(P, B))
     return torch.zeros(n, dtype=torch.uint8, device=device)
@@ -330,7 +335,8 @@ def svt(X, L2, c2: float, tau: float, ws, U=None, s_out=None, warm=False, stream
     """U = SVT(X + c2*L2, tau) (main_LRS_PnP.py:118-124).  method 'tri': tridiagonal eigensolver
     with a certified Jacobi fallback (default); 'jacobi': Jacobi only (warm-startable).  multi_wg:
     the tridiagonal solver's eigenvalue / eigenvector / back-transformation phases over many
-    workgroups (LRS_SVT_MULTI_WG, bit-identical)."""
+    workgroups (LRS_SVT_MULTI_WG, bit-identical).  Wide cubes (256 < B <= svt_max_bands()) always
+    take the Jacobi solver, warm-started when `warm` is set; multi_wg is refused there."""
     L = device_lib()
     _dev(X, torch.float32, "X")
     if L2 is not None:
@@ -377,6 +383,15 @@ def svt_state(ws, P: int, B: int):
     out = (ctypes.c_int * 32)()
     check(device_lib().lrs_diag_svt_state(_p(ws), P, B, ctypes.cast(out, ctypes.c_void_p)), "lrs_diag_svt_state")
     return list(out)
+
+
+def svt_apply_only(X, L2, c2: float, ws, U, stream=None):
+    """U = Z (I - E) alone, with the E the last solve left in `ws`: the apply kernel svt_finish()
+    launches for this band count (diagnostics / timing)."""
+    P, B = X.shape
+    check(device_lib().lrs_diag_svt_apply(_p(X), _p(L2), float(c2), P, B, _p(ws), _p(U), 0, _s(stream)),
+          "lrs_diag_svt_apply")
+    return U
 
 
 def svt_phase_us(ws, P: int, B: int):

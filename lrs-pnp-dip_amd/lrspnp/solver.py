@@ -133,6 +133,18 @@ class LrsPnP:
             D, self.dict_history = learn_dictionary(self.Y, self.M, dcfg, device=dev)
         self.D = f(D)
         self.P, self.B = self.Y.shape
+        # above 256 bands the SVT's eigen stage is the warm-started Jacobi chain, whose warm-start
+        # products read the Gram inside svt_gram(): no all-reduce in between, and the sparse coding
+        # waits for the Gram as it does for svt_method='jacobi'
+        self.svt_wide = cfg.lowrank == "svt" and self.B > 256
+        if self.svt_wide:
+            if self.B > ops.svt_max_bands():
+                raise LrsError(f"lowrank='svt' takes at most {ops.svt_max_bands()} bands, got {self.B}")
+            if comm is not None:
+                raise LrsError(f"a row-slab shard's SVT takes at most 256 bands, got {self.B}: the 256-band limit "
+                               "of sharded SVT (lrs_svt_gram_offset)")
+            if cfg.svt_multi_wg == "on":
+                raise LrsError(f"svt_multi_wg='on' needs at most 256 bands, got {self.B}")
         n, self.K = self.D.shape
         if n != cfg.bb * cfg.bb:
             raise LrsError(f"dictionary has {n} rows, expected bb*bb = {cfg.bb * cfg.bb}")
@@ -307,7 +319,7 @@ class LrsPnP:
                        method=self.cfg.svt_method, multi_wg=mw == "on" or (mw == "auto" and self.comm is not None))
         ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
                    stream=main)
-        if self.cfg.svt_gram_first or self.cfg.svt_method == "jacobi":
+        if self.cfg.svt_gram_first or self.cfg.svt_method == "jacobi" or self.svt_wide:
             # the Gram gets the chip before the sparse-coding kernel fills it, so the ~7 ms Jacobi
             # solve starts at once; the tridiagonal chain fits inside the sparse coding even when
             # its Gram waits for the first sparse-coding workgroups to retire
