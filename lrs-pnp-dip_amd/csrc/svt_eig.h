@@ -1,4 +1,4 @@
-// One-workgroup symmetric eigensolver for the SVT low-rank prox (included by svt.hip).
+// One-workgroup symmetric eigensolver for the SVT low-rank prox (stage 3', B <= 256).
 //
 // The SVT needs E = f(G) = V diag(f(lambda)) V^T of the B x B fp64 Gram G = Z^T Z with
 // f(lambda) = min(tau / sqrt(lambda), 1) (main_LRS_PnP.py:112-124: U = U_s (S - tau)_+ V_h =
@@ -19,7 +19,16 @@
 //   F. E = V f V^T (fp64 accumulation, float32 output, symmetric blocks computed once).
 // Everything runs in ONE workgroup so the chain gets its CU once and never waits for a CU again
 // while the sparse-coding kernel holds the rest of the chip.  The phases are separate
-// (non-inlined) functions so each gets its own register allocation.
+// (non-inlined) functions so each gets its own register allocation.  k_svt_eig is that workgroup;
+// the k_svt_eig_* kernels at the end run the same device functions over several (LRS_SVT_MULTI_WG).
+#pragma once
+
+#include <float.h>
+#include <math.h>
+
+#include "lrs_common.h"
+#include "svt_jacobi.h"
+#include "svt_ws.h"
 
 namespace lrs {
 
@@ -454,8 +463,6 @@ __device__ __forceinline__ void store_fp(float *Fp, int B, int k, int c, float e
 // to 256; the sums run over k in the same order either way).
 constexpr int kEKc = 16;
 __host__ __device__ constexpr int eld(int NB) { return 32 * NB + 1; }
-constexpr int kELd = eld(7);
-__host__ __device__ constexpr int eig_nb(int n) { return n <= 224 ? 7 : 8; }
 
 // stage X(k0 + kk, r) for kk < kEKc, r < LD (zero outside n): KMAJ: X[k * ld + r], else X[r * ld + k]
 template <bool KMAJ, int NB = 7>
@@ -611,6 +618,190 @@ __device__ __noinline__ void eig_ns_step(double *sm, const double *V, const doub
             }
     }
     __syncthreads();
+}
+
+// ---- 3'. the whole eigen chain in one workgroup: tridiagonal path, Jacobi fallback, E ---------
+// V -> w.V[state[1]], eigenvalues -> w.lam, E -> w.E; state[0] = 1 (V valid), state[4] = path.
+// Certificate of the tridiagonal path (else the Jacobi fallback on the same G):
+//   * max |V^T V - I| <= kEigOrth0 before, and <= kEigOrth after <= 3 Newton-Schulz steps;
+//   * per vector, ||T w_i - lambda_i w_i|| plus the mixing the orthogonalisation adds,
+//     0.5 ||((lambda_j - lambda_i) (S - I)_ji)_j||, at most kEigRes * ||T||.
+// E = f(G) then differs from the exact matrix function by O(kEigRes ||T|| max|f'|).
+constexpr double kEigOrth0 = 0.05, kEigOrth = 1e-13, kEigRes = 1e-11;
+
+// packed upper triangle of G (fp64, [n][n] in global) into LDS
+__device__ __forceinline__ void eig_load_packed(const double *G, double *A, int n) {
+    const int tid = threadIdx.x;
+    for (int e0 = tid; e0 < n * n; e0 += 8 * kEigThreads) {
+        double g[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + u * kEigThreads;
+            g[u] = e < n * n ? G[e] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + u * kEigThreads, i = e / n, j = e - i * n;
+            if (e < n * n && j >= i) A[pk_idx(i, j, n)] = g[u];
+        }
+    }
+}
+
+// Gershgorin interval of T (diagonal / first superdiagonal of the packed A), its scale and the
+// Sturm pivot floor (every thread, broadcast reads)
+__device__ __forceinline__ void eig_bounds(const double *A, int n, double &gl, double &gu, double &tn, double &pivmin) {
+    gl = 1e300;
+    gu = -1e300;
+    double emax2 = 0.0;
+    int idx = 0;
+    double ep = 0.0;
+    for (int j = 0; j < n; ++j) {
+        const double e = (j + 1 < n) ? fabs(A[idx + 1]) : 0.0;
+        gl = fmin(gl, A[idx] - ep - e);
+        gu = fmax(gu, A[idx] + ep + e);
+        emax2 = fmax(emax2, e * e);
+        ep = e;
+        if (j + 1 < n) idx += n - j;
+    }
+    tn = fmax(fmax(fabs(gl), fabs(gu)), 1e-300);
+    gl -= 4.0 * DBL_EPSILON * tn * n;
+    gu += 4.0 * DBL_EPSILON * tn * n;
+    pivmin = 1e-290 * fmax(1.0, emax2);
+}
+
+// D + F of the chain (one workgroup): the certificate on V = w.V[0], at most 3 Newton-Schulz
+// steps, the Jacobi fallback, then E.  res = this thread's eigenvector residual (thread i < n).
+// NB: the fp64 products' block count (SvtShape::nb); GA: the fallback's packed triangle in w.T (free
+// once the back-transformation has consumed W) instead of LDS.
+template <int NB, bool GA>
+__device__ __forceinline__ void eig_certify_finish(double *sm, double *red, const SvtWs &w, int n, int B, double tau,
+                                                   double tn, double res) {
+    const int tid = threadIdx.x;
+    int cur = 0;
+    double dev = eig_syrk<true, 1, NB>(sm, w.V[0], n, nullptr, 0.0, 0, nullptr, w.A0, red);
+    bool bad = !(dev <= kEigOrth0);
+    if (!bad) {
+        double mix = 0.0;
+        if (tid < n) {
+            const double li = w.lam[tid];
+            for (int j = 0; j < n; ++j) {
+                const double m = (w.lam[j] - li) * (w.A0[(int64_t)j * n + tid] - (j == tid ? 1.0 : 0.0));
+                mix = __fma_rn(m, m, mix);
+            }
+        }
+        const double bound = res + 0.5 * sqrt(mix);
+        bad = __syncthreads_or(!(bound <= kEigRes * tn));
+    }
+    for (int step = 0; step < 3 && !bad && dev > kEigOrth; ++step) {
+        eig_ns_step<NB>(sm, w.V[cur], w.A0, n, w.V[cur ^ 1]);
+        cur ^= 1;
+        dev = eig_syrk<true, 1, NB>(sm, w.V[cur], n, nullptr, 0.0, 0, nullptr, w.A0, red);
+    }
+    bad = bad || !(dev <= kEigOrth);
+    if (bad) {
+        // clustered / repeated eigenvalues: the orthogonal Jacobi basis of the same G
+        __syncthreads();
+        jacobi_core<GA>(sm, w, w.G, w.T);
+        cur = 0;
+        for (int i0 = 0; i0 < n; i0 += vrebuild_rows(n)) {
+            vrebuild_tile(sm, w, nullptr, w.V[0], i0);
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        w.state[0] = 1;
+        w.state[1] = cur;
+        w.state[4] = bad ? 2 : 1;
+    }
+    __syncthreads();
+    eig_syrk<false, 0, NB>(sm, w.V[cur], n, w.lam, tau, B, w.E, nullptr, red, w.Fp);
+}
+
+// GA (B > kLdsMaxBp): the packed A (reflectors + T) in w.A0, dead once the back-transformation is
+// done (the certificate then writes S there), the LDS holding only the vectors and the products'
+// staging
+template <int NB, bool GA>
+__global__ __launch_bounds__(kEigThreads) void k_svt_eig(SvtWs w, int B, double tau) {
+    extern __shared__ double sm[];
+    __shared__ double shb[2], red[kEigThreads / 64];
+    const int n = (int)w.Bp, tid = threadIdx.x;
+    double *A = GA ? w.A0 : sm;
+    double *pv = GA ? sm : A + (size_t)n * (n + 1) / 2;   // [n] p vector, then the eigenvalues
+    eig_load_packed(w.G, A, n);
+    __syncthreads();
+    eig_tridiag<GA>(A, pv, shb, n, w.beta);
+    double gl, gu, tn, pivmin;
+    eig_bounds(A, n, gl, gu, tn, pivmin);
+    eig_values(A, n, gl, gu, tn, pivmin, pv, w.lam);
+    __syncthreads();
+    const double res = eig_vectors(A, pv, n, tn, w.F, w.T);
+    __syncthreads();
+    for (int k = tid; k < n - 2; k += kEigThreads) pv[k] = w.beta[k];   // the eigenvalues are in w.lam
+    __syncthreads();
+    eig_backtransform(A, pv, n, w.T, w.V[0]);
+    __syncthreads();
+    // certificate + orthogonalisation (LDS of the reflectors is free from here on)
+    eig_certify_finish<NB, GA>(sm, red, w, n, B, tau, tn, res);
+}
+
+// ---- 3''. the same chain over several workgroups (LRS_SVT_MULTI_WG) ---------------------------
+// Phases B (eigenvalues: 4 threads each), C (inverse iteration: a thread per eigenvector) and E
+// (back-transformation: a wave per 4 columns) are independent per eigenvalue / vector / column, so
+// they run on many CUs; A (tridiagonalisation) and D + F (certificate, fallback, E) stay on one
+// workgroup.  Every phase calls the device function k_svt_eig calls, with its workgroup's offset,
+// so the result is bit-identical.  For a caller whose chain is on the critical path (a row-slab
+// shard): beside a chip-filling sparse-coding kernel the one-workgroup chain is the
+// better choice (each launch here waits for free CUs).  Packed A (reflectors + T) passes through
+// w.A0 (free until the certificate), the residuals through w.partial.  One kernel per phase: a kernel
+// trace or HIP events around this chain give the phase times of the one-workgroup chain too.
+template <bool GA>
+__global__ __launch_bounds__(kEigThreads) void k_svt_eig_tri(SvtWs w) {
+    extern __shared__ double sm[];
+    __shared__ double shb[2];
+    const int n = (int)w.Bp, tid = threadIdx.x;
+    double *A = GA ? w.A0 : sm;   // GA: reduced in place in the workspace
+    double *pv = GA ? sm : A + (size_t)n * (n + 1) / 2;
+    eig_load_packed(w.G, A, n);
+    __syncthreads();
+    eig_tridiag<GA>(A, pv, shb, n, w.beta);
+    __syncthreads();
+    if (GA) return;
+    const int np = n * (n + 1) / 2;
+    for (int e = tid; e < np; e += kEigThreads) w.A0[e] = A[e];
+}
+
+constexpr int kEigMwThreads = 64;   // one wave per workgroup for phases B and C (one per CU)
+
+__global__ __launch_bounds__(kEigMwThreads) void k_svt_eig_vals(SvtWs w) {
+    const int n = (int)w.Bp;
+    double gl, gu, tn, pivmin;
+    eig_bounds(w.A0, n, gl, gu, tn, pivmin);
+    eig_values(w.A0, n, gl, gu, tn, pivmin, w.lam, w.lam, kEigMwThreads * blockIdx.x);
+}
+
+__global__ __launch_bounds__(kEigMwThreads) void k_svt_eig_vecs(SvtWs w) {
+    const int n = (int)w.Bp;
+    double gl, gu, tn, pivmin;
+    eig_bounds(w.A0, n, gl, gu, tn, pivmin);
+    const double r = eig_vectors(w.A0, w.lam, n, tn, w.F, w.T, kEigMwThreads * blockIdx.x);
+    const int i = kEigMwThreads * blockIdx.x + threadIdx.x;
+    if (i < n) w.partial[i] = r;
+}
+
+__global__ __launch_bounds__(256) void k_svt_eig_back(SvtWs w) {
+    eig_backtransform(w.A0, w.beta, (int)w.Bp, w.T, w.V[0], 4 * blockIdx.x, 4 * gridDim.x);
+}
+
+template <int NB, bool GA>
+__global__ __launch_bounds__(kEigThreads) void k_svt_eig_cert(SvtWs w, int B, double tau) {
+    extern __shared__ double sm[];
+    __shared__ double red[kEigThreads / 64];
+    const int n = (int)w.Bp, tid = threadIdx.x;
+    const double res = tid < n ? w.partial[tid] : 0.0;
+    double gl, gu, tn, pivmin;
+    eig_bounds(w.A0, n, gl, gu, tn, pivmin);   // from the packed A, before the certificate reuses A0
+    __syncthreads();
+    eig_certify_finish<NB, GA>(sm, red, w, n, B, tau, tn, res);
 }
 
 }  // namespace lrs

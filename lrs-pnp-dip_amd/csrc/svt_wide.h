@@ -1,4 +1,5 @@
-// SVT kernels of the wide-band path, 256 < B <= 512 (included by svt.hip, which holds the dispatch).
+// The wide-band SVT path, 256 < B <= 512: its constants and its Gram kernel (the shape table in
+// svt_ws.h and the launchers in svt.hip hold the dispatch).
 // The one-workgroup kernels of B <= 256 keep every 16 x 16 tile pair of the Gram, and every column
 // of 16 rows of U, in one workgroup's registers; here both products are tiled over a 2-D grid so
 // that a workgroup's accumulators stay below those kernels' however wide the cube is.
@@ -9,6 +10,13 @@
 namespace lrs {
 
 constexpr int kWideMaxBp = 512;
+
+// The apply of wide cubes (k_svt_apply_f<kWideApRows, kWideApTiles, 0>, svt_apply.h): a wave owns
+// 16 RT rows and 16 NTL columns and walks K = B in ceil(B / 8) pairs of k-steps of 4, so Fp holds
+// 2 ceil(B / 8) k-steps.
+__host__ __device__ constexpr int wide_ap_steps(int64_t B) { return 2 * (int)((B + 7) / 8); }
+constexpr int kWideApRows = 2;    // RT: 32 rows per wave, 128 per workgroup
+constexpr int kWideApTiles = 8;   // NTL: 128 columns per workgroup (16 accumulator tiles per wave)
 
 // ---- 1w. Gram G = Z^T Z on the fp64 matrix cores, row slab x column-panel pair ----------------
 // Panels of 64 columns (4 tiles of 16): workgroup (slab, pair (pa <= pb)) stages the slab's rows of
@@ -89,82 +97,6 @@ __global__ __launch_bounds__(256) void k_gram_wide(const float *__restrict__ X, 
             for (int i = 0; i < 4; ++i) out[(int64_t)pi * 256 + (g + 4 * i) * 16 + jl] = acc[b][i];
         }
     }
-}
-
-// ---- 5w. U = Z (I - E) on the f32 matrix cores, row tile x column panel ------------------------
-// k_svt_apply_f with the columns split over blockIdx.y: a wave owns 16 RT rows and 16 NTL columns
-// (RT x NTL accumulator tiles) and walks K = B in ceil(B / 8) pairs of k-steps.  The k-step order
-// and F's fragment layout are k_svt_apply_f's (store_fp: Fp[(st * B + c) * 4 + g], a lane's two A
-// values of a pair are one float2 of its Z row), over 2 ceil(B / 8) k-steps.  Exact f32 products
-// (v_mfma_f32_16x16x4_f32), fp32 accumulation.  Rows >= P, columns >= B and k >= B are predicated:
-// nothing is read past a row's end, and rows k >= B of Fp (never written) are not read.
-__host__ __device__ constexpr int wide_ap_steps(int64_t B) { return 2 * (int)((B + 7) / 8); }
-constexpr int kWideApRows = 2;    // RT: 32 rows per wave, 128 per workgroup
-constexpr int kWideApTiles = 8;   // NTL: 128 columns per workgroup (16 accumulator tiles per wave)
-
-template <int RT, int NTL>
-__global__ __launch_bounds__(256) void k_svt_apply_wide(const float *__restrict__ X, const float *__restrict__ L2,
-                                                        float c2, const float *__restrict__ Fp, int64_t P, int B,
-                                                        float *__restrict__ U) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, jl = lane & 15;
-    const int64_t r0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (16 * RT);
-    if (r0 >= P) return;
-    const int c0 = blockIdx.y * (16 * NTL);
-    floatx4 acc[RT][NTL];
-#pragma unroll
-    for (int m = 0; m < RT; ++m)
-#pragma unroll
-        for (int t = 0; t < NTL; ++t) acc[m][t] = floatx4{0.f, 0.f, 0.f, 0.f};
-    const int nq = (B + 7) / 8;
-    for (int q = 0; q < nq; ++q) {
-        const int k = 8 * q + 2 * g;
-        float2 z[RT];
-#pragma unroll
-        for (int m = 0; m < RT; ++m) {
-            const int64_t row = r0 + 16 * m + jl;
-            z[m] = make_float2(0.f, 0.f);
-            if (row < P && k < B) {
-                if ((B & 1) == 0) {   // even B: 8-byte aligned rows, k + 1 < B
-                    z[m] = *reinterpret_cast<const float2 *>(&X[row * B + k]);
-                    if (L2) {
-                        const float2 l = *reinterpret_cast<const float2 *>(&L2[row * B + k]);
-                        z[m].x = z[m].x + c2 * l.x;   // X + (1/mu_2)*lambda_2
-                        z[m].y = z[m].y + c2 * l.y;
-                    }
-                } else {
-                    z[m].x = X[row * B + k];
-                    if (L2) z[m].x = z[m].x + c2 * L2[row * B + k];
-                    if (k + 1 < B) {
-                        z[m].y = X[row * B + k + 1];
-                        if (L2) z[m].y = z[m].y + c2 * L2[row * B + k + 1];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float *fb = Fp + (int64_t)(2 * q + h) * B * 4 + g;
-#pragma unroll
-            for (int t = 0; t < NTL; ++t) {
-                const int c = c0 + 16 * t + jl;
-                const float b = (c < B && k + h < B) ? fb[c * 4] : 0.0f;
-#pragma unroll
-                for (int m = 0; m < RT; ++m) acc[m][t] = mfma16x16x4(h ? z[m].y : z[m].x, b, acc[m][t]);
-            }
-        }
-    }
-    // acc[m][t][i] = U[r0 + 16m + 4g + i][c0 + 16t + jl]
-#pragma unroll
-    for (int m = 0; m < RT; ++m)
-#pragma unroll
-        for (int t = 0; t < NTL; ++t) {
-            const int c = c0 + 16 * t + jl;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int64_t r = r0 + 16 * m + 4 * g + i;
-                if (r < P && c < B) U[r * B + c] = acc[m][t][i];
-            }
-        }
 }
 
 }  // namespace lrs

@@ -9,7 +9,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# LRSPNP_LIB: another build of the same library (A/B timing of kernel variants, tools/ab_*.sh)
+# LRSPNP_LIB: another build of the same library (A/B timing of kernel variants: tools/gpu.sh steptime)
 LIB_PATH = os.environ.get("LRSPNP_LIB") or os.path.join(_HERE, "liblrspnp_hip.so")
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 
@@ -104,7 +104,7 @@ def _declare(L):
         "lrs_svt_finish_f32": (i32, [vp, vp, f32, i64, i64, f64, vp, vp, i32, vp, sz, vp]),
         "lrs_svt_gram_offset": (i32, [i64, i64, vp, vp]),
         "lrs_diag_svt_state": (i32, [vp, i64, i64, vp]),
-        "lrs_diag_svt_apply": (i32, [vp, vp, f32, i64, i64, vp, vp, i32, vp]),
+        "lrs_diag_svt_apply": (i32, [vp, vp, f32, i64, i64, vp, vp, vp]),
         "lrs_admm_update_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, vp, vp,
                                       vp, vp, f32, f32, f32, vp, vp, vp]),
         # DIP low-rank prox

@@ -378,8 +378,8 @@ def svt_finish(X, L2, c2: float, tau: float, ws, U, s_out=None, warm=False, stre
 
 
 def svt_state(ws, P: int, B: int):
-    """(V valid, V buffer, Jacobi rounds, sweeps, path, -, -, -) of the last SVT call, path 1 =
-    tridiagonal, 2 = Jacobi fallback, 3 = Jacobi (diagnostics; syncs)."""
+    """The 32 state words of the last SVT call: V valid, V buffer, Jacobi rounds, sweeps, path (1 =
+    tridiagonal, 2 = Jacobi fallback, 3 = Jacobi); words 5-31 are spare (diagnostics; syncs)."""
     out = (ctypes.c_int * 32)()
     check(device_lib().lrs_diag_svt_state(_p(ws), P, B, ctypes.cast(out, ctypes.c_void_p)), "lrs_diag_svt_state")
     return list(out)
@@ -389,17 +389,9 @@ def svt_apply_only(X, L2, c2: float, ws, U, stream=None):
     """U = Z (I - E) alone, with the E the last solve left in `ws`: the apply kernel svt_finish()
     launches for this band count (diagnostics / timing)."""
     P, B = X.shape
-    check(device_lib().lrs_diag_svt_apply(_p(X), _p(L2), float(c2), P, B, _p(ws), _p(U), 0, _s(stream)),
+    check(device_lib().lrs_diag_svt_apply(_p(X), _p(L2), float(c2), P, B, _p(ws), _p(U), _s(stream)),
           "lrs_diag_svt_apply")
     return U
-
-
-def svt_phase_us(ws, P: int, B: int):
-    """Phase durations (us) of the last tridiagonal-path solve: load+tridiagonalise, eigenvalues,
-    inverse iteration, back-transformation, certificate/orthogonalisation, fallback+E (syncs)."""
-    st = np.array(svt_state(ws, P, B), dtype=np.int32)
-    t = st[16:32].view(np.uint64).astype(np.float64)
-    return [(t[k + 1] - t[k]) / 100.0 for k in range(6)]
 
 
 def admm_update(X, L1, L2, Y, M, U, phi, bb, grid, gamma, mu1, mu2, norms=None, imout=None, stream=None):

@@ -393,6 +393,20 @@ def test_alpha_kernel_vs_numpy(ops, n, variant):
                                             (3000, 199, 8, 0.02), (3000, 200, 8, 0.02), (5000, 224, 8, 0.02),
                                             (4096, 256, 8, 0.02)])
 def test_svt_kernel_vs_numpy(ops, P, B, rank, noise, method):
+    _svt_vs_numpy(ops, P, B, rank, noise, method)
+
+
+@pytest.mark.parametrize("method", ["tri", "jacobi"])
+@pytest.mark.parametrize("P,B", [(400, 201), (400, 208), (400, 209)])
+def test_svt_shape_class_boundaries(ops, P, B, method):
+    """Both sides of the boundaries between the B <= 256 shape classes (csrc/svt_ws.h): 201 is the first
+    band count of the <16, 64> apply, 208 the last of the <13, 4> Gram, 209 the first of the <16, 8>
+    Gram.  The checks of test_svt_kernel_vs_numpy; the tridiagonal path also over several workgroups,
+    bit for bit."""
+    _svt_vs_numpy(ops, P, B, 8, 0.02, method, multi_wg_too=(method == "tri"))
+
+
+def _svt_vs_numpy(ops, P, B, rank, noise, method, multi_wg_too=False):
     rng = np.random.default_rng(P + B)
     Z = (rng.random((P, rank)) @ rng.random((rank, B)) * 0.3 + noise * rng.standard_normal((P, B)))
     X = Z.astype(np.float32)
@@ -409,6 +423,13 @@ def test_svt_kernel_vs_numpy(ops, P, B, rank, noise, method):
     assert rel(s.cpu().numpy(), sref) < 1e-9
     path = ops.svt_state(ws, P, B)[4]
     assert path == (1 if method == "tri" else 3), path     # the tridiagonal path certified itself
+    if multi_wg_too:
+        wsm = ops.svt_workspace(P, B, "cuda")
+        sm = torch.empty(B, dtype=torch.float64, device="cuda")
+        Um = ops.svt(d(X), d(L2), c2, tau, wsm, s_out=sm, warm=False, method=method, multi_wg=True).cpu().numpy()
+        assert ops.svt_state(wsm, P, B)[4] == path
+        assert np.array_equal(Um.view(np.uint32), U.view(np.uint32))
+        assert np.array_equal(sm.cpu().numpy(), s.cpu().numpy())
     # warm start from the previous eigenvectors on a perturbed matrix
     X2 = (X + 1e-3 * rng.standard_normal((P, B))).astype(np.float32)
     U2 = ops.svt(d(X2), d(L2), c2, tau, ws, warm=True, method=method).cpu().numpy()

@@ -42,5 +42,3 @@ for it in range(iters):
           f"finish {f1:6.3f} ms sweeps {st1[3]} | rel(U_tri - U_jac) {d:.2e}", flush=True)
     s.step()
     torch.cuda.synchronize()
-print("tridiagonal-path phases (us): load+tridiag, eigenvalues, inverse iteration, back-transform, "
-      "certificate+orthogonalise, fallback+E:", [round(v, 1) for v in ops.svt_phase_us(s.svt_ws, s.P, s.B)])
