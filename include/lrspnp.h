@@ -282,7 +282,8 @@ int lrs_admm_update_f32(float *X, float *L1, float *L2, const float *Y, const fl
  *                       (lipschitz_constraint_layer.py:88-122,154-159, 6-22)
  *   lrs_sigma_max_f32   SpectralNorm._update_u_v: torch.svd(W.view(Co,-1))[0]  (:36-44)
  *   lrs_adam_f32        torch.optim.Adam(lr) step                      (…1-LiP.py:215,237)
- *   lrs_masked_mse_f32  MSELoss(target*mask, out*mask) + its gradient  (…1-LiP.py:216,234)
+ *   lrs_masked_mse_f32  MSELoss(target*mask, out*mask) + its gradient  (…1-LiP.py:216,234);
+ *                       _cmask: the same under a per-band mask [C][P]
  *   lrs_es_*            EarlyStop / myMetric variance test             (…1-LiP.py:71-103,244-264)
  *   lrs_dipnet_*        my_Lipschitz_Unet + the get_DIP_out training loop (…1-LiP.py:208-264) */
 #define LRS_PAD_ZERO 0
@@ -355,6 +356,12 @@ int lrs_adam_f32(float *p, const float *g, float *m, float *v, int64_t n, const 
  * mean.  mask (nullable) is [P], broadcast over the C channels. */
 int lrs_masked_mse_f32(const float *out, const float *target, const float *mask, int C, int64_t P,
                        float *gout, double *loss_acc, void *stream);
+/* The same with a mask of mask_channels channels: 1 = [P] (lrs_masked_mse_f32 is this case), C =
+ * per element [C][P], the layout of out and target: a mask that differs between bands (dead
+ * columns, dropped lines, missing bands).  Generalises …1-LiP.py:234, whose mask_bkg is
+ * (1,1,H,W); the mean stays over all C*P elements.  Any other count: LRS_E_INVALID. */
+int lrs_masked_mse_cmask_f32(const float *out, const float *target, const float *mask, int mask_channels,
+                             int C, int64_t P, float *gout, double *loss_acc, void *stream);
 
 /* Layout transforms between the unfolded matrix X[p = i + H j][b] and the DIP image img[b][i][j]
  * (…1-LiP.py:404 DIP_input = X + (1/mu_2) lambda_2 as (1,B,H,W); :411 U back to (P,B)). */
@@ -440,6 +447,14 @@ const float *lrs_dipnet_node_buffer(const lrs_dipnet *net, int node, int which);
 int lrs_dipnet_train_steps(lrs_dipnet *net, const float *x, const float *target, const float *mask,
                            float lr, float beta1, float beta2, float eps, lrs_es_state *es,
                            float *ring, int nsteps, int use_graph, void *stream);
+/* The same with a mask of mask_channels channels: 1 = [P] over the output pixels
+ * (lrs_dipnet_train_steps is this case), the net's output C = per element [C][H][W], for a mask that
+ * differs between bands: loss = MSELoss(target*mask, out*mask) of …1-LiP.py:234 with mask_bkg
+ * generalised from (1,1,H,W) to (1,C,H,W).  Any other count returns LRS_E_INVALID before anything is
+ * launched.  A captured graph is keyed by the mask mode as well as by the pointers. */
+int lrs_dipnet_train_steps_cmask(lrs_dipnet *net, const float *x, const float *target, const float *mask,
+                                 int mask_channels, float lr, float beta1, float beta2, float eps,
+                                 lrs_es_state *es, float *ring, int nsteps, int use_graph, void *stream);
 /* loss of the last step (synchronises the stream; diagnostics only) */
 int lrs_dipnet_last_loss(lrs_dipnet *net, double *loss, void *stream);
 /* Stream ordering between two streams of one device: work enqueued on `waiter` after this call runs

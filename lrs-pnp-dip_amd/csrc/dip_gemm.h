@@ -787,8 +787,11 @@ struct PwArgs {
     int act;   // activation applied after the bias (a conv without BN: its act in the epilogue)
     // the masked-MSE head fused into the network's last conv (tgt != NULL; k_mse_head's arithmetic per
     // element): gz = act'(out) * (-norm (tgt m - out m) m) stored beside out, and per output row the
-    // workgroup's fp64 sums of gz and of (tgt m - out m)^2 in hpart[0 / 1][row][blockIdx.x]
+    // workgroup's fp64 sums of gz and of (tgt m - out m)^2 in hpart[0 / 1][row][blockIdx.x].  The mask
+    // of output row m is read at m * mstride + n: mstride 0 for a [N] pixel mask, N for a per-element
+    // [M][N] one (read like tgt)
     const float *tgt = nullptr, *msk = nullptr;
+    int64_t mstride = 0;
     float *gz = nullptr;
     double *hpart = nullptr;
     float hnorm = 0.0f;
@@ -962,7 +965,8 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
                 *reinterpret_cast<float4 *>(c) = v;
                 if (head) {   // k_mse_head's per-element arithmetic, in the same order
                     const float4 tv = *reinterpret_cast<const float4 *>(a.tgt + (int64_t)m * a.N + n);
-                    const float4 mv = a.msk ? *reinterpret_cast<const float4 *>(a.msk + n) : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+                    const float4 mv = a.msk ? *reinterpret_cast<const float4 *>(a.msk + (int64_t)m * a.mstride + n)
+                                            : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
                     const float oe[4] = {v.x, v.y, v.z, v.w}, te[4] = {tv.x, tv.y, tv.z, tv.w}, me[4] = {mv.x, mv.y, mv.z, mv.w};
                     float ge[4];
 #pragma unroll
@@ -984,7 +988,7 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
                     if (a.act) x = act_fwd(x, a.act);
                     c[u] = x;
                     if (head) {
-                        const float mk = a.msk ? a.msk[n + u] : 1.0f;
+                        const float mk = a.msk ? a.msk[(int64_t)m * a.mstride + n + u] : 1.0f;
                         const float d = a.tgt[(int64_t)m * a.N + n + u] * mk - x * mk;
                         hs[i] += (double)d * (double)d;
                         const float g = act_bwd((-(a.hnorm * d)) * mk, x, a.act);

@@ -1622,21 +1622,24 @@ __global__ void k_sn_apply(const SnConv *convs, const float *scale) {
 
 // ------------------------------------------------------------------------------------------
 // Loss: mse(target*mask, out*mask) over C*P (main_LRS_PnP_DIP_1-LiP.py:234); gout = dL/dout.
-// mask is [P] (broadcast over channels, mask_bkg (1,1,H,W)) or null.
+// mask is null, [P] (mstride 0: broadcast over channels, mask_bkg (1,1,H,W)) or per element [C][P]
+// (mstride P: a mask that differs between bands).  norm stays 2 / (C P) in both: MSELoss's mean.
 // ------------------------------------------------------------------------------------------
 // grid (S, C): workgroup (sb, c) covers pixels [sb*chunk, +chunk) of channel c, so the mask
-// index is the pixel (no 64-bit modulo); vec: float4 loads / stores (P, chunk multiples of 4).
+// index is c * mstride + the pixel (no 64-bit modulo); vec: float4 loads / stores (P, chunk
+// multiples of 4; with mstride = P the mask rows are 16-B aligned as those of out and target are).
 __global__ __launch_bounds__(256) void k_masked_mse(const float *__restrict__ out, const float *__restrict__ target,
-                                                    const float *__restrict__ mask, int C, int64_t P, int chunk,
-                                                    int vec, float *__restrict__ gout, double *loss_acc) {
+                                                    const float *__restrict__ mask, int64_t mstride, int C, int64_t P,
+                                                    int chunk, int vec, float *__restrict__ gout, double *loss_acc) {
     __shared__ double red[8];
     const float norm = (float)(2.0 / ((double)C * (double)P));
     const int64_t off = (int64_t)blockIdx.y * P;
+    const float *mrow = mask ? mask + (int64_t)blockIdx.y * mstride : nullptr;   // this channel's mask row
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(P, i0 + chunk);
     double s = 0.0;
     if (vec) {
         const float4 *o4 = reinterpret_cast<const float4 *>(out + off), *t4 = reinterpret_cast<const float4 *>(target + off);
-        const float4 *m4 = reinterpret_cast<const float4 *>(mask);
+        const float4 *m4 = reinterpret_cast<const float4 *>(mrow);
         float4 *g4 = gout ? reinterpret_cast<float4 *>(gout + off) : nullptr;
         for (int64_t q = (i0 >> 2) + threadIdx.x; q < (i1 >> 2); q += blockDim.x) {
             const float4 ov = o4[q], tv = t4[q];
@@ -1654,7 +1657,7 @@ __global__ __launch_bounds__(256) void k_masked_mse(const float *__restrict__ ou
         }
     } else {
         for (int64_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-            const float mk = mask ? mask[i] : 1.0f;
+            const float mk = mask ? mrow[i] : 1.0f;
             const float a = target[off + i] * mk, b = out[off + i] * mk;
             const float d = a - b;
             s += (double)d * (double)d;
@@ -1675,8 +1678,9 @@ __global__ __launch_bounds__(256) void k_masked_mse(const float *__restrict__ ou
 // (counter cnt[C]) sums the channel losses in order into loss_acc: bias gradient and loss are both
 // deterministic.  Counters are reset by their last arriver.
 __global__ __launch_bounds__(256) void k_mse_head(const float *__restrict__ out, const float *__restrict__ target,
-                                                  const float *__restrict__ mask, int C, int64_t P, int chunk,
-                                                  int vec, int act, float *__restrict__ gz, double *loss_acc,
+                                                  const float *__restrict__ mask, int64_t mstride, int C,
+                                                  int64_t P, int chunk, int vec, int act,
+                                                  float *__restrict__ gz, double *loss_acc,
                                                   double *__restrict__ part, int *__restrict__ cnt,
                                                   float *__restrict__ gbias) {
     __shared__ double red[8];
@@ -1684,13 +1688,14 @@ __global__ __launch_bounds__(256) void k_mse_head(const float *__restrict__ out,
     const float norm = (float)(2.0 / ((double)C * (double)P));
     const int c = blockIdx.y, S = gridDim.x;
     const int64_t off = (int64_t)c * P;
+    const float *mrow = mask ? mask + (int64_t)c * mstride : nullptr;   // as k_masked_mse: [P] or [C][P]
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(P, i0 + chunk);
     double s = 0.0, sb = 0.0;
     if (vec) {
         // one fp64 accumulator pair per float4 lane: four independent dependency chains
         double s4[4] = {0.0, 0.0, 0.0, 0.0}, sb4[4] = {0.0, 0.0, 0.0, 0.0};
         const float4 *o4 = reinterpret_cast<const float4 *>(out + off), *t4 = reinterpret_cast<const float4 *>(target + off);
-        const float4 *m4 = reinterpret_cast<const float4 *>(mask);
+        const float4 *m4 = reinterpret_cast<const float4 *>(mrow);
         float4 *g4 = reinterpret_cast<float4 *>(gz + off);
         const int q0 = (int)(i0 >> 2), q1 = (int)(i1 >> 2);
         // two float4 per thread per trip: both loads of both in flight together
@@ -1721,7 +1726,7 @@ __global__ __launch_bounds__(256) void k_mse_head(const float *__restrict__ out,
         sb = (sb4[0] + sb4[1]) + (sb4[2] + sb4[3]);
     } else {
         for (int64_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-            const float mk = mask ? mask[i] : 1.0f;
+            const float mk = mask ? mrow[i] : 1.0f;
             const float o = out[off + i];
             const float d = target[off + i] * mk - o * mk;
             s += (double)d * (double)d;

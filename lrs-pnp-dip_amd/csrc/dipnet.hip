@@ -498,6 +498,7 @@ static const PwKernel kPwKernels[] = {
 // 2 per CU instead of 1.2 rounds at 64 (A/B: -10 us per step).
 struct PwHead {   // the fused masked-MSE head of a network's last conv (PwArgs::tgt)
     const float *tgt, *msk;
+    int64_t mstride;   // mask row stride: 0 ([P], every channel) or P ([C][P])
     float *gz;
     double *hpart;
     float norm;
@@ -535,6 +536,7 @@ int pw_launch(const __bf16 *A, int64_t pstride, int lda, int M, const float *B, 
     if (head) {
         ah.tgt = head->tgt;
         ah.msk = head->msk;
+        ah.mstride = head->msk ? head->mstride : 0;
         ah.gz = head->gz;
         ah.hpart = head->hpart;
         ah.hnorm = head->norm;
@@ -1093,19 +1095,37 @@ extern "C" int lrs_adam_f32(float *p, const float *g, float *m, float *v, int64_
     return LRS_OK;
 }
 
-extern "C" int lrs_masked_mse_f32(const float *out, const float *target, const float *mask, int C, int64_t P,
-                                  float *gout, double *loss_acc, void *stream) {
+// The mask's channel count (1: [P], broadcast over the channels; C: per element [C][P]) -> its row
+// stride in floats (0 / P; 0 without a mask); -1 for any other count.
+static int64_t mask_stride(const float *mask, int mask_channels, int C, int64_t P) {
+    if (mask_channels != 1 && mask_channels != C) return -1;
+    return (mask && mask_channels == C && C > 1) ? P : 0;
+}
+
+// float4 mask loads: row c starts at mask + c * mstride, 16-B aligned for every c when the base is
+// and the stride is a multiple of 4 floats (0, or P with P % 4 == 0)
+static bool mask_al16(const float *mask, int64_t mstride) { return !mask || (al16(mask) && mstride % 4 == 0); }
+
+extern "C" int lrs_masked_mse_cmask_f32(const float *out, const float *target, const float *mask, int mask_channels,
+                                        int C, int64_t P, float *gout, double *loss_acc, void *stream) {
     if (!out || !target || !loss_acc || C <= 0 || P <= 0) return LRS_E_INVALID;
-    const int vec = (P % 4 == 0 && al16(out) && al16(target) && (!mask || al16(mask)) && (!gout || al16(gout))) ? 1 : 0;
+    const int64_t mstride = mask_stride(mask, mask_channels, C, P);
+    if (mstride < 0) return LRS_E_INVALID;
+    const int vec = (P % 4 == 0 && al16(out) && al16(target) && mask_al16(mask, mstride) && (!gout || al16(gout))) ? 1 : 0;
     int64_t S = (512 + C - 1) / C;   // ~512 workgroups over the C channels (fewer loss atomics)
     S = std::max<int64_t>(1, std::min<int64_t>(S, (P + 1023) / 1024));
     int64_t chunk = (P + S - 1) / S;
     if (vec) chunk = (chunk + 3) & ~(int64_t)3;
     if (chunk > INT32_MAX || C > 65535) return LRS_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_masked_mse, dim3((unsigned)S, (unsigned)C), dim3(256), 0, (hipStream_t)stream, out, target,
-                       mask, C, P, (int)chunk, vec, gout, loss_acc);
+                       mask, mstride, C, P, (int)chunk, vec, gout, loss_acc);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
+}
+
+extern "C" int lrs_masked_mse_f32(const float *out, const float *target, const float *mask, int C, int64_t P,
+                                  float *gout, double *loss_acc, void *stream) {
+    return lrs_masked_mse_cmask_f32(out, target, mask, 1, C, P, gout, loss_acc, stream);
 }
 
 extern "C" int lrs_unfolded_to_image_f32(const float *X, const float *L, float c, int64_t H, int64_t W, int64_t B,
@@ -1205,8 +1225,9 @@ struct lrs_dipnet {
     std::vector<hipEvent_t> ev_fork;
     hipEvent_t ev_join = nullptr;
     int64_t part2_off = 0;   // the side stream's split-K partials
-    struct Key {
+    struct Key {   // (no padding: compared with memcmp)
         const void *x, *t, *m, *es, *ring;
+        int64_t mstride;   // the mask mode: [P] and [C][P] at one pointer are different graphs
         float lr, b1, b2, eps;
     } key{};
     bool have_key = false;
@@ -1397,14 +1418,16 @@ struct EsJob {   // the early-stopping update of this step's output, run beside 
 int es_update(const float *out, int64_t N, float *ring, lrs_es_state *es, hipStream_t st);
 int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_done = false, AdamPend *pw = nullptr,
                     bool head_reduce = false, const EsJob *esj = nullptr);
-int mse_head(lrs_dipnet *net, const float *out, const float *target, const float *mask, hipStream_t st);
+int mse_head(lrs_dipnet *net, const float *out, const float *target, const float *mask, int64_t mstride,
+             hipStream_t st);
 
 // k_mse_head over the last node (conv without BN): gz and the bias gradient of that node, + loss
-int mse_head(lrs_dipnet *net, const float *out, const float *target, const float *mask, hipStream_t st) {
+int mse_head(lrs_dipnet *net, const float *out, const float *target, const float *mask, int64_t mstride,
+             hipStream_t st) {
     const auto &N = net->nodes.back();
     float *gz = net->f(N.gz_off);
     const int64_t P = N.P;
-    const int vec = (P % 4 == 0 && al16(out) && al16(target) && (!mask || al16(mask)) && al16(gz)) ? 1 : 0;
+    const int vec = (P % 4 == 0 && al16(out) && al16(target) && mask_al16(mask, mstride) && al16(gz)) ? 1 : 0;
     int64_t S = bn_split(P);   // ~4096 pixels per workgroup
     int64_t chunk = (P + S - 1) / S;
     if (vec) chunk = (chunk + 3) & ~(int64_t)3;
@@ -1412,15 +1435,16 @@ int mse_head(lrs_dipnet *net, const float *out, const float *target, const float
     // partials: bias [C][S], loss [C][S], channel losses [C]  (bn_part_doubles = 3 C bn_split(P))
     if (chunk > INT32_MAX || P > INT32_MAX || 2 * (int64_t)N.C * S + N.C > bn_part_doubles(N.C, P))
         return LRS_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_mse_head, dim3((unsigned)S, (unsigned)N.C), dim3(256), 0, st, out, target, mask, N.C, P,
-                       (int)chunk, vec, N.d.act, gz, net->loss_acc(), net->bnpart(), net->headcnt(),
+    hipLaunchKernelGGL(k_mse_head, dim3((unsigned)S, (unsigned)N.C), dim3(256), 0, st, out, target, mask, mstride, N.C,
+                       P, (int)chunk, vec, N.d.act, gz, net->loss_acc(), net->bnpart(), net->headcnt(),
                        net->grads + N.b_off);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
 
-int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const float *mask, float lr, float b1, float b2,
-                float eps, lrs_es_state *es, float *ring, hipStream_t st) {
+// mstride: the mask's row stride (mask_stride: 0 for a [P] mask or none, P for a [C][P] one)
+int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const float *mask, int64_t mstride, float lr,
+                float b1, float b2, float eps, lrs_es_state *es, float *ring, hipStream_t st) {
     // the weight-preparation launch at the head of the forward also zeroes the loss accumulator
     // and advances Adam's step counter (read only by this step's k_adam); without one, a tiny launch
     const bool folded = net->n_prep > 0;
@@ -1456,9 +1480,11 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
     const auto &Lst = net->nodes[n - 1];
     // the loss head in the last conv's epilogue (k_pw): gz, and per-workgroup sums for the bias gradient
     // and the loss, reduced in the backward on the side stream (k_mse_head's arithmetic per element)
-    const PwHead hd{target, mask, net->f(Lst.gz_off), net->hpart(), (float)(2.0 / ((double)Lst.C * (double)Lst.P)),
-                    &net->head_nwg};
-    const bool fused_head = net->head_pw && (!mask || al16(mask)) && al16(target);
+    const PwHead hd{target, mask, mstride, net->f(Lst.gz_off), net->hpart(),
+                    (float)(2.0 / ((double)Lst.C * (double)Lst.P)), &net->head_nwg};
+    // (k_pw's epilogue takes its float4 form when P % 4 == 0 and reads the mask rows as float4 there;
+    // a [C][P] mask with P % 4 != 0 has unaligned rows and takes k_mse_head's scalar path instead)
+    const bool fused_head = net->head_pw && mask_al16(mask, mstride) && al16(target);
     int rc = dipnet_forward(net, x, st, folded, overlap, fused_head ? &hd : nullptr);
     if (rc) return rc;
     const float *out = net->f(Lst.out_off);
@@ -1466,9 +1492,10 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
     if (fused_head) {
         rc = LRS_OK;
     } else if (net->head_fusable) {
-        rc = mse_head(net, out, target, mask, st);
+        rc = mse_head(net, out, target, mask, mstride, st);
     } else {
-        rc = lrs_masked_mse_f32(out, target, mask, Lst.C, Lst.P, net->f(Lst.grad_off), net->loss_acc(), st);
+        rc = lrs_masked_mse_cmask_f32(out, target, mask, mstride ? Lst.C : 1, Lst.C, Lst.P, net->f(Lst.grad_off),
+                                      net->loss_acc(), st);
     }
     if (rc) return rc;
     // the input conv's weight-gradient split-K sum is finished inside Adam (one launch less on the
@@ -2121,26 +2148,29 @@ static int ensure_side(lrs_dipnet *net, hipStream_t st) {
     return (int)e;
 }
 
-extern "C" int lrs_dipnet_train_steps(lrs_dipnet *net, const float *x, const float *target, const float *mask,
-                                      float lr, float beta1, float beta2, float eps, lrs_es_state *es, float *ring,
-                                      int nsteps, int use_graph, void *stream) {
+extern "C" int lrs_dipnet_train_steps_cmask(lrs_dipnet *net, const float *x, const float *target, const float *mask,
+                                            int mask_channels, float lr, float beta1, float beta2, float eps,
+                                            lrs_es_state *es, float *ring, int nsteps, int use_graph, void *stream) {
     if (!net || !net->ws || !x || !target || nsteps < 0 || (es && !ring)) return LRS_E_INVALID;
+    const int64_t mstride = mask_stride(mask, mask_channels, net->nodes.back().C, net->nodes.back().P);
+    if (mstride < 0) return LRS_E_INVALID;   // before anything is launched
     hipStream_t st = (hipStream_t)stream;
     if (const int rs = ensure_side(net, (hipStream_t)stream)) return rs;
     if (!use_graph) {
         for (int s = 0; s < nsteps; ++s) {
-            const int rc = dipnet_step(net, x, target, mask, lr, beta1, beta2, eps, es, ring, st);
+            const int rc = dipnet_step(net, x, target, mask, mstride, lr, beta1, beta2, eps, es, ring, st);
             if (rc) return rc;
         }
         return LRS_OK;
     }
     if (!st) return LRS_E_INVALID;   // capture needs a non-default stream
-    const lrs_dipnet::Key k{x, target, mask, es, ring, lr, beta1, beta2, eps};
+    const lrs_dipnet::Key k{x, target, mask, es, ring, mstride, lr, beta1, beta2, eps};
+    static_assert(sizeof(lrs_dipnet::Key) == 5 * sizeof(void *) + sizeof(int64_t) + 4 * sizeof(float), "Key has padding");
     if (!net->have_key || memcmp(&k, &net->key, sizeof(k)) != 0) {
         drop_graph(net);
         hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
         if (e != hipSuccess) return (int)e;
-        const int rc = dipnet_step(net, x, target, mask, lr, beta1, beta2, eps, es, ring, st);
+        const int rc = dipnet_step(net, x, target, mask, mstride, lr, beta1, beta2, eps, es, ring, st);
         hipGraph_t g = nullptr;
         e = hipStreamEndCapture(st, &g);
         if (rc) {
@@ -2162,6 +2192,12 @@ extern "C" int lrs_dipnet_train_steps(lrs_dipnet *net, const float *x, const flo
         if (e != hipSuccess) return (int)e;
     }
     return LRS_OK;
+}
+
+extern "C" int lrs_dipnet_train_steps(lrs_dipnet *net, const float *x, const float *target, const float *mask,
+                                      float lr, float beta1, float beta2, float eps, lrs_es_state *es, float *ring,
+                                      int nsteps, int use_graph, void *stream) {
+    return lrs_dipnet_train_steps_cmask(net, x, target, mask, 1, lr, beta1, beta2, eps, es, ring, nsteps, use_graph, stream);
 }
 
 extern "C" int lrs_dipnet_last_loss(lrs_dipnet *net, double *loss, void *stream) {

@@ -52,6 +52,8 @@ def dip_opts(precision: int = DIP_SPLIT_BF16, upsample_dgrad: int = 0) -> DipOpt
 
 _lib = None
 _device_checked = False
+# the entry points that take a per-band mask [C][P] (the only ones a variant build may lack)
+_PER_BAND_MASK = ("lrs_masked_mse_cmask_f32", "lrs_dipnet_train_steps_cmask")
 
 
 def build(force: bool = False) -> str:
@@ -128,6 +130,7 @@ def _declare(L):
         "lrs_diag_sigma_phases": (i32, [c.POINTER(vp), c.POINTER(c.c_int), c.POINTER(c.c_int), i32, vp, sz, vp, vp]),
         "lrs_adam_f32": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, vp]),
         "lrs_masked_mse_f32": (i32, [vp, vp, vp, i32, i64, vp, vp, vp]),
+        "lrs_masked_mse_cmask_f32": (i32, [vp, vp, vp, i32, i32, i64, vp, vp, vp]),
         "lrs_unfolded_to_image_f32": (i32, [vp, vp, f32, i64, i64, i64, vp, vp]),
         "lrs_image_to_unfolded_f32": (i32, [vp, i64, i64, i64, vp, vp]),
         "lrs_es_ring_bytes": (sz, [i32, i64]),
@@ -153,10 +156,13 @@ def _declare(L):
         "lrs_dipnet_grads": (c.c_size_t, [vp]),
         "lrs_dipnet_node_buffer": (c.c_size_t, [vp, i32, i32]),
         "lrs_dipnet_train_steps": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
+        "lrs_dipnet_train_steps_cmask": (i32, [vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
         "lrs_dipnet_last_loss": (i32, [vp, c.POINTER(f64), vp]),
         "lrs_stream_wait": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
+        if name in _PER_BAND_MASK and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
+            continue   # an A/B build from before the per-band masks: its [P] paths still time against this one
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

@@ -87,3 +87,28 @@ def synthetic_cube(H: int, W: int, B: int, seed: int = 0, rank: int = 8, noise_s
         mask = np.tile(bm, reps)[:H, :W]
     obs = (noisy * mask[None]).astype(np.float32)
     return obs, clean.astype(np.float32), mask.astype(np.float32)
+
+
+def stripe_mask(H: int, W: int, B: int, seed: int = 0, col_frac: float = 0.04, pixel_frac: float = 0.03,
+                missing_band: int | bool | None = None) -> np.ndarray:
+    """Seeded band-varying sensor mask (B, H, W), float32 0 / 1: what a push-broom instrument leaves.
+
+    Per band: round(col_frac * W) (at least one) dead image columns at positions drawn per band
+    (striping / dead detector elements, which differ between bands), and dead pixels with
+    probability pixel_frac.  missing_band: an index, or True for a seeded choice, zeroes that whole
+    band (a dropped band); None keeps every band.  The defaults leave 90-95 % of the entries
+    observed (the regime of the reference's low_rank_sparsity_mask), not counting a missing band.
+    The solver's mask matrix is M = unfold(stripe_mask(...)) (P, B).  Host only."""
+    if not (H > 0 and W > 0 and B > 0 and 0 <= col_frac < 1 and 0 <= pixel_frac < 1):
+        raise ValueError("stripe_mask: H, W, B > 0 and fractions in [0, 1)")
+    rng = np.random.default_rng(seed)
+    ncol = min(W - 1, max(1, int(round(col_frac * W)))) if col_frac > 0 else 0
+    m = (rng.uniform(size=(B, H, W)) >= pixel_frac).astype(np.float32)
+    for b in range(B):
+        m[b][:, rng.choice(W, ncol, replace=False)] = 0.0
+    if missing_band is not None and missing_band is not False:
+        mb = int(rng.integers(B)) if missing_band is True else int(missing_band)
+        if not 0 <= mb < B:
+            raise ValueError(f"stripe_mask: missing_band {mb} outside [0, {B})")
+        m[mb] = 0.0
+    return m

@@ -294,16 +294,38 @@ class DipNet:
                     eps: float = 1e-8, es=None, use_graph: bool = False):
         """nsteps of: forward, masked MSE, backward, Adam (and the ES update when es is given).
         use_graph: replay one captured hipGraph per step instead of the eager launches (bit-identical,
-        measured slower: DESIGN.md §5 -- off by default, as in DipConfig)."""
+        measured slower: DESIGN.md §5 -- off by default, as in DipConfig).
+        mask: None, a pixel mask (P,) / (H, W) applied to every band, or a per-band mask (C, H, W) of
+        the output's shape; the mode is chosen from the element count (LrsError for any other)."""
         import torch
+        mc = self.mask_channels(mask)
         stream_wait(self.stream, torch.cuda.current_stream())
-        rc = self.L.lrs_dipnet_train_steps(
-            self.h, _ptr(x), _ptr(target), _ptr(mask), ctypes.c_float(lr), ctypes.c_float(betas[0]),
-            ctypes.c_float(betas[1]), ctypes.c_float(eps), _ptr(es.state) if es else None,
-            _ptr(es.ring) if es else None, int(nsteps), 1 if use_graph else 0,
-            ctypes.c_void_p(self.stream.cuda_stream))
+        tail = (ctypes.c_float(lr), ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(eps),
+                _ptr(es.state) if es else None, _ptr(es.ring) if es else None, int(nsteps), 1 if use_graph else 0,
+                ctypes.c_void_p(self.stream.cuda_stream))
+        if mc == 1:
+            rc = self.L.lrs_dipnet_train_steps(self.h, _ptr(x), _ptr(target), _ptr(mask), *tail)
+        else:
+            rc = self.L.lrs_dipnet_train_steps_cmask(self.h, _ptr(x), _ptr(target), _ptr(mask), mc, *tail)
         _check(rc, "lrs_dipnet_train_steps")
         stream_wait(torch.cuda.current_stream(), self.stream)
+
+    def mask_channels(self, mask) -> int:
+        """1 for no mask or a pixel mask (P elements), C for a per-band mask (C*P elements) of this
+        net's output; LrsError for any other size, or a mask the engine cannot read in place."""
+        import torch
+        C, H, W = self.out_shape
+        if mask is None:
+            return 1
+        n = mask.numel()
+        if n not in (H * W, C * H * W):
+            raise _lib.LrsError(f"mask has {n} elements ({tuple(mask.shape)}): expected a pixel mask ({H * W},) / "
+                                f"({H}, {W}) or a per-band mask ({C}, {H}, {W})")
+        if n == H * W:
+            return 1
+        if mask.dtype != torch.float32 or not mask.is_cuda or not mask.is_contiguous():
+            raise _lib.LrsError("a per-band mask must be a contiguous float32 tensor on the device")
+        return C
 
     def node_buffer(self, node: int, which: int = 0):
         """A copy of node `node`'s workspace buffer (0 output, 1 pre-BN z, 2 dL/dz, 3 dL/d(output);
@@ -399,6 +421,8 @@ class DipProx:
             early_stop: bool = True):
         """Train a freshly initialised net on (dip_input -> target under mask) and return the output
         at the early-stopping epoch (or after num_iter steps with early_stop=False).
+        mask: (P,) / (H, W), one pixel mask for every band (the reference's mask_bkg), or (C, H, W),
+        a mask per band (DipNet.train_steps).
 
         The result is a view of an engine buffer, valid until the next call; it is ordered after
         the caller's current stream (the caller's stream waits for the DIP stream on return)."""
@@ -406,6 +430,7 @@ class DipProx:
         cfg = self.cfg
         n_iter = cfg.num_iter if num_iter is None else num_iter
         net = self.net
+        net.mask_channels(mask)   # a mask of neither shape is refused before anything is enqueued
         stream_wait(net.stream, torch.cuda.current_stream())
         net.init_params(self.calls if seed is None else seed)
         self.calls += 1

@@ -15,7 +15,7 @@ from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLA
                    device_lib, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "masked_mse", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -426,3 +426,40 @@ def image_to_unfolded(img, H: int, W: int, out=None, stream=None):
     out = out if out is not None else torch.empty((H * W, B), dtype=torch.float32, device=img.device)
     check(Ld.lrs_image_to_unfolded_f32(_p(img), H, W, B, _p(out), _s(stream)), "lrs_image_to_unfolded_f32")
     return out
+
+
+def mask_channels(mask, C: int, P: int) -> int:
+    """The mode of a DIP loss mask for a C x P output: 1 for a pixel mask (P elements, applied to every
+    channel), C for a per-element mask (C*P elements, the layout of the output: a mask that differs
+    between bands); None (no mask) counts as 1.  Anything else is refused."""
+    if mask is None:
+        return 1
+    n = mask.numel()
+    if n == P:
+        return 1
+    if n == C * P:
+        return C
+    raise LrsError(f"mask has {n} elements ({tuple(mask.shape)}): expected a pixel mask (H, W) / (P,) with "
+                   f"{P} or a per-band mask (C, H, W) with {C * P}")
+
+
+def masked_mse(out, target, mask=None, want_grad: bool = True, stream=None):
+    """MSELoss(target*mask, out*mask) over the C x P elements of out (C, ...) and its gradient dL/dout
+    (…1-LiP.py:234).  mask: None, P elements (every channel) or C*P elements (per band).
+    Returns (loss: float64 device scalar, gout or None)."""
+    Ld = device_lib()
+    _dev(out, torch.float32, "out")
+    _dev(target, torch.float32, "target")
+    if target.shape != out.shape or out.dim() < 2:
+        raise LrsError(f"out {tuple(out.shape)} and target {tuple(target.shape)} must be the same (C, ...) shape")
+    C = out.shape[0]
+    P = out.numel() // C
+    if mask is not None:
+        _dev(mask, torch.float32, "mask")
+    mc = mask_channels(mask, C, P)
+    gout = torch.empty_like(out) if want_grad else None
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        acc = torch.zeros(1, dtype=torch.float64, device=out.device)   # the kernel accumulates the sum
+        check(Ld.lrs_masked_mse_cmask_f32(_p(out), _p(target), _p(mask), mc, C, P, _p(gout), _p(acc), _s(stream)),
+              "lrs_masked_mse_cmask_f32")
+        return acc / (C * P), gout

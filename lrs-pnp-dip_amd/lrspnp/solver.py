@@ -237,8 +237,14 @@ class LrsPnP:
                                  stream_priority=self.cfg.lowrank_priority) if engine else None
         self.dip_target = torch.empty((self.B, H, W), dtype=torch.float32, device=dev)
         ops.unfolded_to_image(self.Y, None, 1.0, H, W, self.dip_target)
-        pix = ops.unfolded_to_image(self.M[:, :1].contiguous(), None, 1.0, H, W)   # (1, H, W)
-        self.dip_mask = pix.reshape(-1).contiguous()
+        # The reference's mask_bkg is one (1,1,H,W) pixel mask.  A mask M that differs between bands
+        # (dead columns, dropped lines, missing bands) goes to the loss per element instead, as
+        # (B, H, W): the mask the caller passed is the specification (one device check, here only).
+        if bool((self.M == self.M[:, :1]).all()):
+            pix = ops.unfolded_to_image(self.M[:, :1].contiguous(), None, 1.0, H, W)   # (1, H, W)
+            self.dip_mask = pix.reshape(-1).contiguous()
+        else:
+            self.dip_mask = ops.unfolded_to_image(self.M, None, 1.0, H, W)             # (B, H, W)
         self.dip_in = torch.empty_like(self.dip_target)
         self.dip_steps = []
 

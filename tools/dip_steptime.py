@@ -27,6 +27,8 @@ ap.add_argument("--es", action="store_true", help="with the device early-stoppin
                                                    "patience 60), as get_DIP_out runs with early stopping on")
 ap.add_argument("--dump", default=None, help="also save the net output after the timed rounds (.npy): "
                                               "bit-for-bit A/B of output-preserving kernel changes")
+ap.add_argument("--bandmask", action="store_true", help="a band-varying mask (lrspnp.data.stripe_mask, (bands, hw, "
+                                                         "hw)): the loss heads' per-element [C][P] mode")
 a = ap.parse_args()
 nodes = lipschitz_unet_nodes(a.bands, a.bands, 128) if a.net == "unet" else skip_nodes(a.bands, a.bands)
 net = DipNet(nodes, a.bands, a.hw, a.hw, stream_priority=a.priority)
@@ -35,6 +37,9 @@ g = torch.Generator(device="cuda").manual_seed(0)
 x = torch.rand(a.bands, a.hw, a.hw, device="cuda", generator=g)
 t = torch.rand(a.bands, a.hw, a.hw, device="cuda", generator=g)
 m = (torch.rand(a.hw, a.hw, device="cuda", generator=g) > 0.2).float()
+if a.bandmask:
+    from lrspnp.data import stripe_mask
+    m = torch.from_numpy(stripe_mask(a.hw, a.hw, a.bands, 0)).cuda()
 es = None
 if a.es:
     from lrspnp.dip import EarlyStopper
