@@ -516,6 +516,66 @@ def test_unet_gradients_implicit_sizes_vs_fp64(L, upsample_dgrad):
             assert rel(gg, gr) < max(1e-4, 2 * rel(g32, gr)) and rel(beg, ber) < max(1e-4, 2 * rel(be32, ber)), i
 
 
+@pytest.mark.parametrize("H", [12, 132])
+def test_workspace_alignment_offset_by_4_vs_fp64(L, H):
+    """The half of a node's plan that lrs_dipnet_bind completes from the workspace's 16-byte alignment.
+    A three-conv 1-Lip chain (stride-2 3 x 3, 3 x 3, 1 x 1 without BatchNorm; split-bf16) on an 8 x H x H
+    input is bound twice with the same parameters, input, target and pixel mask: to an aligned workspace, and
+    to a buffer of lrs_dipnet_workspace() + 16 bytes offset by 4.  Each runs 3 eager training steps; the
+    third step's output and parameter gradients are compared with the fp64 restatement at the parameters
+    the engine held after its second step, with the bound of test_unet_gradients_implicit_sizes_vs_fp64:
+    1e-4, or twice the fp32-torch error.  (Each against the oracle, not against each other bitwise: the
+    float4 kernels give way to the scalar ones.)  H = 12: 6 x 6 maps, where both BatchNorms run inside the
+    direct conv launch and the alignment changes only the scalar / float4 forms inside the launchers;
+    H = 132: 66 x 66 maps of 4356 pixels, where the aligned binding takes the register BatchNorm k_bn_fwd_r
+    and the offset one the generic kernels."""
+    from gen_dip_golden import flat_params
+    from lrspnp.dip import BN_NONE, DipNet, conv_node
+    C = 8
+    units = [conv_node(0, 0, 16, 3, 2), conv_node(1, 0, 16, 3), conv_node(2, 0, C, 1, bn=BN_NONE)]
+    Ho = H // 2
+    flat = torch.from_numpy(flat_params(units, 33, C, H, H))
+    g = torch.Generator().manual_seed(8)
+    x, t = torch.rand(C, H, H, generator=g), torch.rand(C, Ho, Ho, generator=g)
+    m = (torch.rand(Ho * Ho, generator=g) > 0.1).float()
+    offs, _ = dip_ref.param_offsets(units, C, H, H)
+    for shift in (0, 4):
+        net = DipNet(units, C, H, H)
+        if shift:
+            nbytes = int(L.lrs_dipnet_workspace(net.h))
+            buf = torch.zeros(nbytes + 16, dtype=torch.uint8, device="cuda")
+            net.ws = buf[shift:shift + nbytes]
+            assert net.ws.data_ptr() % 16 == shift
+            rc = L.lrs_dipnet_bind(net.h, P(net.params), P(net.grads), P(net.exp_avg), P(net.exp_avg_sq), P(net.bnstats),
+                                   P(net.ws), nbytes)
+            assert rc == 0
+        net.params.copy_(flat.cuda())
+        net.reset_optimizer()
+        net.train_steps(x.cuda(), t.cuda(), m.cuda(), 2, lr=0.01, use_graph=False)   # LrsError unless LRS_OK
+        torch.cuda.synchronize()
+        p2 = net.params.cpu().clone()
+        net.train_steps(x.cuda(), t.cuda(), m.cuda(), 1, lr=0.01, use_graph=False)
+        torch.cuda.synchronize()
+        out, gd = net.output().cpu(), net.grads.cpu()
+        ref = {}
+        for dt in (torch.float64, torch.float32):
+            p = p2.to(dt).clone().requires_grad_(True)
+            o = dip_ref.forward(p, units, x.to(dt))
+            dip_ref.loss_fn(o, t.to(dt), m.to(dt)).backward()
+            ref[dt] = (o.detach().double(), p.grad.double())
+        (o64, g64), (o32, g32) = ref[torch.float64], ref[torch.float32]
+        print("shift", shift, "H", H, "out", rel(out, o64), rel(o32, o64))
+        assert rel(out, o64) < max(1e-4, 2 * rel(o32, o64)), shift
+        for i in range(len(units)):
+            Wg, bg, gg, beg = dip_ref.views(gd, units, i, offs, C, H, H)
+            Wr, br, gr, ber = dip_ref.views(g64, units, i, offs, C, H, H)
+            W32, b32, ga32, be32 = dip_ref.views(g32, units, i, offs, C, H, H)
+            print("  node", i, rel(Wg, Wr), rel(W32, Wr))
+            assert rel(Wg, Wr) < max(1e-4, 2 * rel(W32, Wr)), (shift, i, rel(Wg, Wr), rel(W32, Wr))
+            if gg is not None:
+                assert rel(gg, gr) < max(1e-4, 2 * rel(ga32, gr)) and rel(beg, ber) < max(1e-4, 2 * rel(be32, ber)), (shift, i)
+
+
 def _grads_vs_fp64_on_gpu(nodes, flat, x, t, m, net, c0, H, W):
     """Step-0 gradient of the engine against the restatement in fp64 and fp32 torch on the GPU (TF32
     off): per parameter tensor, (engine error, fp32-torch error) relative to fp64."""
