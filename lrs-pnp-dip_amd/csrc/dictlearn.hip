@@ -8,20 +8,16 @@
 // The sparse-coding half of a round is lrs_ista_f32 / lrs_ista_pat_f32, unchanged.
 //
 // The three products (A D^T: nb x K x n, R^T A: n x nb x K, A^T A: K x nb x K) run on the bf16 matrix
-// cores with the three-term split of dip_gemm.h: every fp32 operand value is split exactly into
-// hi + mid + lo bf16 terms when its tile is written to LDS, and the six partial products with
-// i + j <= 2 accumulate smallest first in fp32 (v_mfma_f32_16x16x32_bf16).  One kernel, k_dl_gemm,
+// cores as fp32-accurate split-bf16 products (lrs_split.h): every fp32 operand value is split into its
+// three bf16 terms when its tile is written to LDS.  One kernel, k_dl_gemm,
 // serves all three through its operand strides; the mask, the subtraction and the squared residual
 // are the first product's epilogue.  The two products that sum over the nb blocks are split over
 // that sum into fixed chunks whose partials are added in chunk order (fp64), the objective and the
 // column norms are fp64 sums in a fixed order: no floating-point atomics, so two runs on the same
 // inputs give the same bits.  c is read from device memory; nothing synchronises the host.
-#include "lrs_common.h"
+#include "lrs_split.h"
 
 namespace lrs {
-
-typedef __bf16 dlbf8 __attribute__((ext_vector_type(8)));
-typedef float dlf4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDlTile = 64;   // output tile per 256-thread workgroup (2 x 2 waves of 32 x 32)
 constexpr int kDlK = 32;      // k per step (one MFMA)
@@ -69,12 +65,15 @@ __device__ __forceinline__ void dl_load(const float *__restrict__ S, int64_t sx,
     }
 }
 
-// exact three-term bf16 split (dip_gemm.h s3_split) of the 8 values, one 16-B LDS write per plane
+// the three bf16 planes of the 8 values, one 16-B LDS write per plane.  The arithmetic is split_bf16's
+// (lrs_split.h) and must follow it; it is spelled out here, hi and mid placed before lo is formed,
+// because through split_bf16x8 both k_dl_gemm instantiations schedule these conversions differently
+// (same instructions, other order and registers) and the device code is held fixed.
 template <bool KC>
 __device__ __forceinline__ void dl_store(__bf16 (*T)[kDlTile][kDlLd], const float (&v)[8]) {
     const int t = threadIdx.x;
     const int row = KC ? (t >> 2) : (t & 63), kb = 8 * (KC ? (t & 3) : (t >> 6));
-    dlbf8 p0, p1, p2;
+    bf16x8 p0, p1, p2;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float x = v[e];
@@ -85,24 +84,13 @@ __device__ __forceinline__ void dl_store(__bf16 (*T)[kDlTile][kDlLd], const floa
         p1[e] = b1;
         p2[e] = (__bf16)(r1 - (float)b1);
     }
-    *reinterpret_cast<dlbf8 *>(&T[0][row][kb]) = p0;
-    *reinterpret_cast<dlbf8 *>(&T[1][row][kb]) = p1;
-    *reinterpret_cast<dlbf8 *>(&T[2][row][kb]) = p2;
-}
-
-__device__ __forceinline__ dlf4 dl_mfma6(const dlbf8 (&A)[3], const dlbf8 (&B)[3], dlf4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[2], B[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[0], acc, 0, 0, 0);
-    return acc;
+    *reinterpret_cast<bf16x8 *>(&T[0][row][kb]) = p0;
+    *reinterpret_cast<bf16x8 *>(&T[1][row][kb]) = p1;
+    *reinterpret_cast<bf16x8 *>(&T[2][row][kb]) = p2;
 }
 
 // blockIdx.x = M tile, blockIdx.y = N tile, blockIdx.z = chunk of the summed dimension.
-// v_mfma_f32_16x16x32_bf16: lane l supplies A[l & 15][8 (l >> 4) + 0..7] and B[8 (l >> 4) + 0..7][l & 15];
-// the accumulator holds C[4 (l >> 4) + r][l & 15] (cdna_hip_programming.md §3).
+// (the MFMA's lane layout: split_mfma6, lrs_split.h)
 template <bool AKC, bool BKC, bool RESID>
 __global__ __launch_bounds__(256) void k_dl_gemm(DlGemm g) {
     __shared__ __attribute__((aligned(16))) __bf16 As[3][kDlTile][kDlLd];
@@ -113,11 +101,11 @@ __global__ __launch_bounds__(256) void k_dl_gemm(DlGemm g) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int wm = (wv >> 1) * 32, wn = (wv & 1) * 32;
     const int jl = lane & 15, gk = lane >> 4;
-    dlf4 acc[2][2];
+    floatx4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = dlf4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 2; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     float va[8], vb[8];
     dl_load<AKC>(g.A, g.sam, g.sak, g.M, m0, kbeg, kend, va);
     dl_load<BKC>(g.B, g.sbn, g.sbk, g.N, n0, kbeg, kend, vb);
@@ -129,18 +117,18 @@ __global__ __launch_bounds__(256) void k_dl_gemm(DlGemm g) {
             dl_load<AKC>(g.A, g.sam, g.sak, g.M, m0, k0 + kDlK, kend, va);
             dl_load<BKC>(g.B, g.sbn, g.sbk, g.N, n0, k0 + kDlK, kend, vb);
         }
-        dlbf8 fa[2][3], fb[2][3];
+        bf16x8 fa[2][3], fb[2][3];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
-                fa[a][p] = *reinterpret_cast<const dlbf8 *>(&As[p][wm + 16 * a + jl][8 * gk]);
-                fb[a][p] = *reinterpret_cast<const dlbf8 *>(&Bs[p][wn + 16 * a + jl][8 * gk]);
+                fa[a][p] = *reinterpret_cast<const bf16x8 *>(&As[p][wm + 16 * a + jl][8 * gk]);
+                fb[a][p] = *reinterpret_cast<const bf16x8 *>(&Bs[p][wn + 16 * a + jl][8 * gk]);
             }
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) acc[a][b] = dl_mfma6(fa[a], fb[b], acc[a][b]);
+            for (int b = 0; b < 2; ++b) acc[a][b] = split_mfma6(fa[a], fb[b], acc[a][b]);
         __syncthreads();
     }
     if constexpr (RESID) {

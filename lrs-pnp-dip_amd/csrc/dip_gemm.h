@@ -1,10 +1,8 @@
 // Split-bf16 GEMM and implicit-GEMM convolution for the DIP engine (gfx950).
 //
-// C[M][N] = op(A)[M][K] op(B)[K][N] in fp32 accuracy on the bf16 matrix cores: every fp32 operand
-// value is split exactly into three bf16 terms (hi + mid + lo, the remainder after lo is below
-// 2^-24 relative) ONCE, when its tile is written to LDS, and each 16x16 output tile accumulates
-// the six partial products with i + j <= 2 (A_lo B_hi, A_mid B_mid, A_hi B_lo, A_mid B_hi,
-// A_hi B_mid, A_hi B_hi; smallest first) with v_mfma_f32_16x16x32_bf16 into fp32.
+// C[M][N] = op(A)[M][K] op(B)[K][N] in fp32 accuracy on the bf16 matrix cores (lrs_split.h): every
+// fp32 operand value is split into its three bf16 terms ONCE, when its tile is written to LDS, and
+// each 16x16 output tile accumulates the six-product chain (split_mfma6) into fp32.
 //
 // Tile: 128 x 128 per 256-thread workgroup (2 x 2 waves of 64 x 64 = 4 x 4 MFMA tiles), 32 k
 // per step.  LDS holds the three bf16 planes of both operands k-contiguous, 64 B rows with the
@@ -21,12 +19,11 @@
 #pragma once
 
 #include "lrs_dip.h"
+#include "lrs_split.h"
 
 namespace lrs {
 
 constexpr int kS3K = 32;
-typedef __bf16 s3bf8 __attribute__((ext_vector_type(8)));
-typedef float s3f4 __attribute__((ext_vector_type(4)));
 
 // LDS image of one operand: [plane][row 0..127][32 k] bf16, chunk (8 k) swizzled per row
 struct S3Tile {
@@ -51,57 +48,24 @@ __device__ __forceinline__ int s3_row() { return KC ? (threadIdx.x >> 1) : (thre
 template <bool KC>
 __device__ __forceinline__ int s3_kb() { return KC ? 16 * (threadIdx.x & 1) : 16 * (threadIdx.x >> 7); }
 
-struct S3Split {
-    __bf16 b0, b1, b2;
-};
-__device__ __forceinline__ S3Split s3_split(float x) {
-    S3Split r;
-    r.b0 = (__bf16)x;
-#ifdef LRS_S3_CHEAPSPLIT   // timing experiment only (wrong products): the split's VALU cost
-    r.b1 = r.b0;
-    r.b2 = r.b0;
-    return r;
-#endif
-    const float r1 = x - (float)r.b0;
-    r.b1 = (__bf16)r1;
-    r.b2 = (__bf16)(r1 - (float)r.b1);
-    return r;
-}
-
 template <bool KC>
 __device__ __forceinline__ void s3_store(S3Tile &T, const float (&v)[16]) {
     const int row = s3_row<KC>(), c0 = s3_kb<KC>() >> 3;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        s3bf8 p0, p1, p2;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const S3Split q = s3_split(v[8 * h + e]);
-            p0[e] = q.b0;
-            p1[e] = q.b1;
-            p2[e] = q.b2;
-        }
+        bf16x8 p0, p1, p2;
+        split_bf16x8(&v[8 * h], p0, p1, p2);
         const int ch = s3_chunk(row, c0 + h) * 8;
-        *reinterpret_cast<s3bf8 *>(&T.v[0][row][ch]) = p0;
-        *reinterpret_cast<s3bf8 *>(&T.v[1][row][ch]) = p1;
-        *reinterpret_cast<s3bf8 *>(&T.v[2][row][ch]) = p2;
+        *reinterpret_cast<bf16x8 *>(&T.v[0][row][ch]) = p0;
+        *reinterpret_cast<bf16x8 *>(&T.v[1][row][ch]) = p1;
+        *reinterpret_cast<bf16x8 *>(&T.v[2][row][ch]) = p2;
     }
 }
 
-__device__ __forceinline__ void s3_frag(const S3Tile &T, int row, int gk, s3bf8 (&f)[3]) {
+__device__ __forceinline__ void s3_frag(const S3Tile &T, int row, int gk, bf16x8 (&f)[3]) {
     const int ch = s3_chunk(row, gk) * 8;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const s3bf8 *>(&T.v[p][row][ch]);
-}
-
-__device__ __forceinline__ s3f4 s3_mfma6(const s3bf8 (&A)[3], const s3bf8 (&B)[3], s3f4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[2], B[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[0], acc, 0, 0, 0);
-    return acc;
+    for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const bf16x8 *>(&T.v[p][row][ch]);
 }
 
 // ---- loaders ---------------------------------------------------------------------------------
@@ -313,7 +277,7 @@ __device__ __forceinline__ void wlp_store(S3Tile &T, const float (&v)[16]) {
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
         const int row = wlp_row(u), at = s3_chunk(row, k >> 3) * 8 + (k & 7);
-        const S3Split q = s3_split(v[u]);
+        const Bf16Split q = split_bf16(v[u]);
         T.v[0][row][at] = q.b0;
         T.v[1][row][at] = q.b1;
         T.v[2][row][at] = q.b2;
@@ -581,23 +545,23 @@ __device__ __forceinline__ void gemm_s3_body(const GemmArgs &g, LA la, LB lb, S3
     lb.setup(n0, tab, cls);
     if constexpr (PREP) lb.prepare(kbeg, kend, 0);
     __syncthreads();
-    s3f4 acc[4][4];
+    floatx4 acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = s3f4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     float va[16], vb[16];
     static_assert(!LB::pre, "B is never pre-split");
     auto mma = [&]() {
-        s3bf8 fb[4][3];
+        bf16x8 fb[4][3];
 #pragma unroll
         for (int b = 0; b < 4; ++b) s3_frag(Bs, wn + 16 * b + jl, gk, fb[b]);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            s3bf8 fa[3];
+            bf16x8 fa[3];
             s3_frag(As, wm + 16 * a + jl, gk, fa);
 #pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = s3_mfma6(fa, fb[b], acc[a][b]);
+            for (int b = 0; b < 4; ++b) acc[a][b] = split_mfma6(fa, fb[b], acc[a][b]);
         }
     };
     if constexpr (PREP) {
@@ -832,18 +796,12 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
         for (int i = 0; i < 8; ++i) {
             const int c = c0 + 4 * i;
             if (c >= nck) break;
-            s3bf8 p0, p1, p2;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const S3Split q = s3_split(v[i][u]);
-                p0[u] = q.b0;
-                p1[u] = q.b1;
-                p2[u] = q.b2;
-            }
+            bf16x8 p0, p1, p2;
+            split_bf16x8(v[i], p0, p1, p2);
             char *dst = pw_smem + (int64_t)n * a.ldsrow + 16 * c;
-            *reinterpret_cast<s3bf8 *>(dst) = p0;
-            *reinterpret_cast<s3bf8 *>(dst + plane) = p1;
-            *reinterpret_cast<s3bf8 *>(dst + 2 * plane) = p2;
+            *reinterpret_cast<bf16x8 *>(dst) = p0;
+            *reinterpret_cast<bf16x8 *>(dst + plane) = p1;
+            *reinterpret_cast<bf16x8 *>(dst + 2 * plane) = p2;
         }
     } else {   // NPX pixels x nck chunks as items it = t + 256 j: pixel it % NPX, chunk it / NPX
         const __amdgpu_buffer_rsrc_t rs = s3_rsrc(a.B, (int)(a.K * a.N * 4));
@@ -864,30 +822,24 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
         for (int j = 0; j < kMaxIt; ++j) {
             const int it = t + 256 * j, n = it % NPX, c = it / NPX;
             if (it >= items) break;
-            s3bf8 p0, p1, p2;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const S3Split q = s3_split(v[j][u]);
-                p0[u] = q.b0;
-                p1[u] = q.b1;
-                p2[u] = q.b2;
-            }
+            bf16x8 p0, p1, p2;
+            split_bf16x8(v[j], p0, p1, p2);
             char *dst = pw_smem + (int64_t)n * a.ldsrow + 16 * c;
-            *reinterpret_cast<s3bf8 *>(dst) = p0;
-            *reinterpret_cast<s3bf8 *>(dst + plane) = p1;
-            *reinterpret_cast<s3bf8 *>(dst + 2 * plane) = p2;
+            *reinterpret_cast<bf16x8 *>(dst) = p0;
+            *reinterpret_cast<bf16x8 *>(dst + plane) = p1;
+            *reinterpret_cast<bf16x8 *>(dst + 2 * plane) = p2;
         }
     }
-    s3f4 acc[MT][NB];
+    floatx4 acc[MT][NB];
 #pragma unroll
     for (int j = 0; j < MT; ++j)
 #pragma unroll
-        for (int b = 0; b < NB; ++b) acc[j][b] = s3f4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < NB; ++b) acc[j][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     const int ksteps = a.Kp32 / 32;
-    s3bf8 fa[MT][3], fn[MT][3];
+    bf16x8 fa[MT][3], fn[MT][3];
     // A fragments: 16-B buffer loads (L2-resident planes), rows >= M and k >= lda at kOob (zeros)
     const __amdgpu_buffer_rsrc_t ra = s3_rsrc(a.A, (int)(3 * a.pstride * 2));
-    auto loadA = [&](int ks, s3bf8 (&f)[MT][3]) {
+    auto loadA = [&](int ks, bf16x8 (&f)[MT][3]) {
         const int k = ks * 32 + 8 * gk;
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
@@ -895,7 +847,7 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
             const int vo = (row < a.M && k < a.lda) ? 2 * (row * a.lda + k) : kOob;
 #pragma unroll
             for (int p = 0; p < 3; ++p)
-                f[j][p] = __builtin_bit_cast(s3bf8, __builtin_amdgcn_raw_buffer_load_b128(ra, vo, (int)(2 * p * a.pstride), 0));
+                f[j][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, vo, (int)(2 * p * a.pstride), 0));
         }
     };
     // NB = 4 prefetches the next k-step's A fragments; NB = 5 has no registers for that (its loads
@@ -909,17 +861,17 @@ __global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
         } else if (ks > 0) {
             loadA(ks, fa);
         }
-        s3bf8 fb[NB][3];
+        bf16x8 fb[NB][3];
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const char *s0 = pw_smem + (int64_t)(16 * b + jl) * a.ldsrow + 16 * (4 * ks + gk);
 #pragma unroll
-            for (int p = 0; p < 3; ++p) fb[b][p] = *reinterpret_cast<const s3bf8 *>(s0 + p * plane);
+            for (int p = 0; p < 3; ++p) fb[b][p] = *reinterpret_cast<const bf16x8 *>(s0 + p * plane);
         }
 #pragma unroll
         for (int j = 0; j < MT; ++j)
 #pragma unroll
-            for (int b = 0; b < NB; ++b) acc[j][b] = s3_mfma6(fa[j], fb[b], acc[j][b]);
+            for (int b = 0; b < NB; ++b) acc[j][b] = split_mfma6(fa[j], fb[b], acc[j][b]);
         if (PF && ks + 1 < ksteps) {
 #pragma unroll
             for (int j = 0; j < MT; ++j)
@@ -1090,7 +1042,7 @@ __device__ __forceinline__ void conv_prep_body(const ConvPrep &c, float s, int64
     // planes reach 2^31 / 3 elements)
     const int nf = c.wf ? c.Cout * (c.upc ? 16 : c.kk) * c.Cp : 0, nd = c.wd ? c.Cin * ed * c.Cop : 0;
     auto put = [&](__bf16 *dst, int plane, int j, float x) {
-        const S3Split q = s3_split(x);
+        const Bf16Split q = split_bf16(x);
         dst[j] = q.b0;
         dst[plane + j] = q.b1;
         dst[2 * plane + j] = q.b2;

@@ -299,7 +299,9 @@ __global__ void k_gemm_reduce(const float *__restrict__ part, int nsplit, int M,
 //   padded coordinate iy in [0, Hu + 2 pad);  col[(c*k + ky)*k + kx][oy*Wo + ox] =
 //   xsrc(c, iy = oy*stride + ky, ix = ox*stride + kx)   (torch weight order [co][ci][ky][kx])
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect_idx(int u, int n) {   // ReflectionPad2d (no edge repeat)
+// ReflectionPad2d (no edge repeat) folded once: for -n < u < 2n - 1, which pad < n guarantees.
+// (ista_prox.h's reflect_idx is the periodic numpy 'reflect' for any overhang: another function.)
+__device__ __forceinline__ int reflect_once_idx(int u, int n) {
     if (u < 0) u = -u;
     if (u >= n) u = 2 * (n - 1) - u;
     return u;
@@ -318,8 +320,8 @@ __global__ __launch_bounds__(256) void k_im2col(const float *__restrict__ x, Con
         float v = 0.0f;
         bool inside = true;
         if (gm.pad_mode == LRS_PAD_REFLECT) {
-            uy = reflect_idx(uy, gm.Hu);
-            ux = reflect_idx(ux, gm.Wu);
+            uy = reflect_once_idx(uy, gm.Hu);
+            ux = reflect_once_idx(ux, gm.Wu);
         } else {
             inside = uy >= 0 && uy < gm.Hu && ux >= 0 && ux < gm.Wu;
         }
@@ -403,40 +405,13 @@ __global__ __launch_bounds__(256) void k_col2im(const float *__restrict__ dcol, 
 }
 
 // ------------------------------------------------------------------------------------------
-// Wave / block reductions.  Doubles go through DPP row operations (no LDS crossbar): after four
-// steps every 16-lane row holds its row sum, then readlane gathers the four rows.
+// Block reductions over wave_sum_butterfly (lrs_common.h: DPP row operations, no LDS crossbar).
 // ------------------------------------------------------------------------------------------
-// (full-row permutations only: every lane reads a lane of its own row, so no 'old' value is needed
-// -- mov_dpp instead of update_dpp(0, ...) saves the zeroing of each destination)
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_mov_dpp((int)(b & 0xffffffffLL), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xF, 0xF, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// sum over the 64 lanes, result uniform (fixed order: deterministic)
-__device__ __forceinline__ double wave_sum_d(double v) {
-    v += dpp_d<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_d<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_d<0x141>(v);   // row_half_mirror
-    v += dpp_d<0x140>(v);   // row_mirror
-    return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
-}
-
 // block sum; red must hold 2 * (blockDim/64) doubles; `parity` alternates between calls so a
 // single barrier suffices (the other half of red is still being read by slow waves)
 __device__ __forceinline__ double block_sum_d1(double v, double *red, int &parity) {
     const int nw = blockDim.x >> 6;
-    v = wave_sum_d(v);
+    v = wave_sum_butterfly(v);
     double *r = red + parity * nw;
     if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -458,8 +433,8 @@ __device__ __forceinline__ double block_sum_d(double v, double *red) {
 // 0.0), so the results are bitwise those of consecutive block_sum_d1 calls; every thread gets them.
 __device__ __forceinline__ void block_sum2_d(double &a, double &b, double *red) {
     const int nw = blockDim.x >> 6, w = threadIdx.x >> 6;
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
+    a = wave_sum_butterfly(a);
+    b = wave_sum_butterfly(b);
     if ((threadIdx.x & 63) == 0) {
         red[w] = a;
         red[nw + w] = b;
@@ -476,9 +451,9 @@ __device__ __forceinline__ void block_sum2_d(double &a, double &b, double *red) 
 
 __device__ __forceinline__ void block_sum3_d(double &a, double &b, double &c, double *red) {
     const int nw = blockDim.x >> 6, w = threadIdx.x >> 6;
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    c = wave_sum_d(c);
+    a = wave_sum_butterfly(a);
+    b = wave_sum_butterfly(b);
+    c = wave_sum_butterfly(c);
     if ((threadIdx.x & 63) == 0) {
         red[w] = a;
         red[nw + w] = b;
@@ -1515,15 +1490,15 @@ __global__ __launch_bounds__(256) void k_sn_sigma(const SnConv *convs, const dou
         // sum over the row block's 8 lanes (xor 1, xor 2, then lane i + lane 7 - i)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            u4[i] += dpp_d<0xB1>(u4[i]);
-            u4[i] += dpp_d<0x4E>(u4[i]);
-            u4[i] += dpp_d<0x141>(u4[i]);
+            u4[i] += dpp_perm_f64<0xB1>(u4[i]);
+            u4[i] += dpp_perm_f64<0x4E>(u4[i]);
+            u4[i] += dpp_perm_f64<0x141>(u4[i]);
         }
         const int own = cb & 3;   // (selects, not a branch per lane group)
         const double u01 = (own & 1) ? u4[1] : u4[0], u23 = (own & 1) ? u4[3] : u4[2];
         double u = (own & 2) ? u23 : u01;
-        const double w_rr = wave_sum_d(half == 0 ? rr * rr : 0.0);
-        const double w_ru = wave_sum_d(half == 0 ? rr * u : 0.0);
+        const double w_rr = wave_sum_butterfly(half == 0 ? rr * rr : 0.0);
+        const double w_ru = wave_sum_butterfly(half == 0 ? rr * u : 0.0);
         if ((t & 63) == 0) {
             red2[0][(t >> 6) + 4 * par] = w_rr;
             red2[1][(t >> 6) + 4 * par] = w_ru;
@@ -1954,8 +1929,8 @@ __global__ void k_es_decide(const float *ring, int64_t N, int nblk, lrs_es_state
         dq += part[b];
         qa += part[kEsMaxBlocks + b];
     }
-    dq = wave_sum_d(dq);   // fixed order
-    qa = wave_sum_d(qa);
+    dq = wave_sum_butterfly(dq);   // fixed order
+    qa = wave_sum_butterfly(qa);
     if (threadIdx.x != 0) return;
     const int epoch = st->count;           // iteration index i of the reference loop
     const double q = (epoch == 0 || es_refresh(epoch, S)) ? dq : *q2 + dq;

@@ -45,24 +45,18 @@ __device__ __forceinline__ void sm_store_pre(SmImg &T, int row, int kg, const ui
 }
 
 __device__ __forceinline__ void sm_store_f32(SmImg &T, int row, int kg, const float (&v)[8]) {
-    s3bf8 p0, p1, p2;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const S3Split q = s3_split(v[e]);
-        p0[e] = q.b0;
-        p1[e] = q.b1;
-        p2[e] = q.b2;
-    }
+    bf16x8 p0, p1, p2;
+    split_bf16x8(v, p0, p1, p2);
     const int ch = sm_chunk(row, kg) * 8;
-    *reinterpret_cast<s3bf8 *>(&T.v[0][row][ch]) = p0;
-    *reinterpret_cast<s3bf8 *>(&T.v[1][row][ch]) = p1;
-    *reinterpret_cast<s3bf8 *>(&T.v[2][row][ch]) = p2;
+    *reinterpret_cast<bf16x8 *>(&T.v[0][row][ch]) = p0;
+    *reinterpret_cast<bf16x8 *>(&T.v[1][row][ch]) = p1;
+    *reinterpret_cast<bf16x8 *>(&T.v[2][row][ch]) = p2;
 }
 
-__device__ __forceinline__ void sm_frag(const SmImg &T, int row, int c, s3bf8 (&f)[3]) {
+__device__ __forceinline__ void sm_frag(const SmImg &T, int row, int c, bf16x8 (&f)[3]) {
     const int ch = sm_chunk(row, c) * 8;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const s3bf8 *>(&T.v[p][row][ch]);
+    for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const bf16x8 *>(&T.v[p][row][ch]);
 }
 
 // A: pre-split planes, plane p of row x at P + p * pstride + x * ld (k contiguous, K and ld
@@ -239,11 +233,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_sm(GemmArgs g, LA la, LB lb) {
     const int jl = lane & 15, gk = lane >> 4;
     lb.setup(n0, tab);
     __syncthreads();
-    s3f4 acc[2][2];
+    floatx4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = s3f4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 2; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     SmAReg<LA> ha[2];
     float vb[2][8];
     auto lda = [&](int k0, int j) {
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_sm(GemmArgs g, LA la, LB lb) {
         }
 #pragma unroll
         for (int s = 0; s < kSmK / 32; ++s) {
-            s3bf8 fa[2][3], fb[2][3];
+            bf16x8 fa[2][3], fb[2][3];
 #pragma unroll
             for (int a = 0; a < 2; ++a) sm_frag(As, wm + 16 * a + jl, 4 * s + gk, fa[a]);
 #pragma unroll
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_sm(GemmArgs g, LA la, LB lb) {
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = s3_mfma6(fa[a], fb[b], acc[a][b]);
+                for (int b = 0; b < 2; ++b) acc[a][b] = split_mfma6(fa[a], fb[b], acc[a][b]);
         }
         __syncthreads();
     }

@@ -28,6 +28,7 @@
 //  * the NLM prox runs in fp64 on the accumulator layout (a lane holds 4 consecutive atoms per tile).
 #include "ista_paths.h"
 #include "lrs_nlm.h"
+#include "lrs_split.h"
 
 namespace lrs {
 
@@ -314,21 +315,14 @@ __global__ __launch_bounds__(kIstaThreads, 2) void k_ista_res(IstaParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Split-bf16 resident kernel (n_pad <= 64, K = 256).  The two products per inner iteration run on
-// the bf16 matrix cores (v_mfma_f32_16x16x32_bf16, 16x the f32 MFMA rate, and unlike the f32
-// MFMA not on the VALU's FMA datapath) with every fp32 operand split exactly into three bf16
-// terms, v = v1 + v2 + v3 (8 significand bits each: 24 = fp32); the six products with
-// i + j <= 4 are kept (the dropped ones are <= 2^-24 relative), accumulated in fp32, so each
-// product has fp32-GEMM accuracy (not the bitwise f32 MFMA result; parity is held to the same
-// 1e-5 relative L2 as the rest of the pipeline).
+// Split-bf16 resident kernel (n_pad <= 64, K = 256).  The two products per inner iteration are
+// fp32-accurate products on the bf16 matrix cores (lrs_split.h: the split, the chain, the accuracy).
 //   * D lives in LDS once, as three bf16 images [row][atom] with 8-byte chunks XOR-swizzled per
 //     row; the first product reads its A fragments by rows (ds_read_b64), the second reads the
 //     same images transposed (ds_read_b64_tr_b16): 96 KB instead of the f32 kernel's 136 KB;
 //   * accumulators feed the next product's B operand directly (C rows 4g..4g+3 of two 16-tiles
 //     = the 8 k-values of lane group g), as in the f32 kernel.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 
 template <int K>
@@ -347,14 +341,6 @@ __device__ __forceinline__ int b3_off(int row, int chunk) {   // element offset 
     return row * K + 4 * (chunk ^ b3_swz(row));
 }
 
-__device__ __forceinline__ void split3(float v, __bf16 &a, __bf16 &b, __bf16 &c) {
-    a = (__bf16)v;
-    const float r1 = v - (float)a;
-    b = (__bf16)r1;
-    const float r2 = r1 - (float)b;
-    c = (__bf16)r2;
-}
-
 constexpr int kB3Waves = 4;                       // one wave per SIMD: the whole 512-entry register file
 constexpr int kB3Threads = kB3Waves * kWave;
 
@@ -363,12 +349,11 @@ __device__ __forceinline__ void stage_dictionary_b3(IstaSmemB3<K> &S, const floa
     for (int idx = threadIdx.x; idx < kStageRows * K; idx += kB3Threads) {
         const int r = idx / K, a = idx % K;
         const float v = r < n ? D[(int64_t)r * K + a] : 0.0f;
-        __bf16 h, m, l;
-        split3(v, h, m, l);
+        const Bf16Split s = split_bf16(v);
         const int o = b3_off<K>(r, a >> 2) + (a & 3);
-        S.D[0][0][o] = h;
-        S.D[1][0][o] = m;
-        S.D[2][0][o] = l;
+        S.D[0][0][o] = s.b0;
+        S.D[1][0][o] = s.b1;
+        S.D[2][0][o] = s.b2;
     }
 }
 
@@ -376,27 +361,11 @@ __device__ __forceinline__ void stage_dictionary_b3(IstaSmemB3<K> &S, const floa
 __device__ __forceinline__ void split_frag(const float (&u)[4], const float (&w)[4], bf16x8 (&f)[3]) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        __bf16 a, b, c;
-        split3(u[e], a, b, c);
-        f[0][e] = a; f[1][e] = b; f[2][e] = c;
-        split3(w[e], a, b, c);
-        f[0][e + 4] = a; f[1][e + 4] = b; f[2][e + 4] = c;
+        const Bf16Split a = split_bf16(u[e]);
+        f[0][e] = a.b0; f[1][e] = a.b1; f[2][e] = a.b2;
+        const Bf16Split b = split_bf16(w[e]);
+        f[0][e + 4] = b.b0; f[1][e + 4] = b.b1; f[2][e + 4] = b.b2;
     }
-}
-
-__device__ __forceinline__ floatx4 mfma_bf(const bf16x8 &a, const bf16x8 &b, floatx4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// acc += A B with both split three ways, small terms first
-__device__ __forceinline__ floatx4 mfma_split6(const bf16x8 (&A)[3], const bf16x8 (&B)[3], floatx4 acc) {
-    acc = mfma_bf(A[2], B[0], acc);
-    acc = mfma_bf(A[1], B[1], acc);
-    acc = mfma_bf(A[0], B[2], acc);
-    acc = mfma_bf(A[1], B[0], acc);
-    acc = mfma_bf(A[0], B[1], acc);
-    acc = mfma_bf(A[0], B[0], acc);
-    return acc;
 }
 
 __device__ __forceinline__ bf16x8 cat4(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
@@ -419,7 +388,7 @@ __device__ __forceinline__ floatx4 b3_gemm2(const IstaSmemB3<K> &S, int q, const
                 (lds_s4 *)(&S.D[sp][0][b3_off<K>(r1, 4 * q + pp)]));
             A[sp] = cat4(__builtin_bit_cast(bf16x4, a0), __builtin_bit_cast(bf16x4, a1));
         }
-        acc = mfma_split6(A, rf[pr], acc);
+        acc = split_mfma6(A, rf[pr], acc);
     }
     return acc;
 }
@@ -439,7 +408,7 @@ __device__ __forceinline__ void b3_gemm1(const IstaSmemB3<K> &S, int p, const bf
             const bf16x4 a1 = *reinterpret_cast<const bf16x4 *>(&S.D[sp][0][b3_off<K>(row, 8 * p + 4 + g)]);
             A[sp] = cat4(a0, a1);
         }
-        R[t] = mfma_split6(A, xf, R[t]);
+        R[t] = split_mfma6(A, xf, R[t]);
     }
 }
 
@@ -578,12 +547,11 @@ __device__ __forceinline__ void stage_dictionary_tm(IstaSmemB3<K> &S, const floa
     for (int idx = threadIdx.x; idx < kStageRows * K; idx += kB3Threads) {
         const int r = idx / K, a = idx % K;
         const float v = r < n ? D[(int64_t)r * K + a] : 0.0f;
-        __bf16 h, m, l;
-        split3(v, h, m, l);
+        const Bf16Split s = split_bf16(v);
         const int o = tm_off(r, a >> 2) + (a & 3);
-        S.D[0][0][o] = h;
-        S.D[1][0][o] = m;
-        S.D[2][0][o] = l;
+        S.D[0][0][o] = s.b0;
+        S.D[1][0][o] = s.b1;
+        S.D[2][0][o] = s.b2;
     }
 }
 
@@ -646,7 +614,7 @@ __device__ __forceinline__ floatx4 tm_gemm2(const IstaSmemB3<K> &S, int q, const
     for (int pr = 0; pr < 2; ++pr) {
         Frag3 F;
         ln_load_unit<K>(S, LnUnit{1, q, pr}, A, F);
-        acc = mfma_split6(F.a, rf[pr], acc);
+        acc = split_mfma6(F.a, rf[pr], acc);
     }
     return acc;
 }
@@ -658,7 +626,7 @@ __device__ __forceinline__ void tm_gemm1(const IstaSmemB3<K> &S, int p, const bf
     for (int t = 0; t < 4; ++t) {
         Frag3 F;
         ln_load_unit<K>(S, LnUnit{2, t, p}, A, F);
-        R[t] = mfma_split6(F.a, xf, R[t]);
+        R[t] = split_mfma6(F.a, xf, R[t]);
     }
 }
 
@@ -774,8 +742,8 @@ __global__ __launch_bounds__(kB3Threads, 1) void k_ista_ln2(IstaParams p) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const LnUnit U = ln_unit(pp, k, u);
-                    if (U.kind == 1) G[U.a] = mfma_split6(F[cur][u].a, rf[U.b], U.b == 0 ? floatx4{0.f, 0.f, 0.f, 0.f} : G[U.a]);
-                    else if (U.kind == 2) R[U.a] = mfma_split6(F[cur][u].a, xf, R[U.a]);
+                    if (U.kind == 1) G[U.a] = split_mfma6(F[cur][u].a, rf[U.b], U.b == 0 ? floatx4{0.f, 0.f, 0.f, 0.f} : G[U.a]);
+                    else if (U.kind == 2) R[U.a] = split_mfma6(F[cur][u].a, xf, R[U.a]);
                 }
                 // operands of the next slot
                 const int pn = (k == 3) ? pp + 1 : pp, kn = (k + 1) & 3;

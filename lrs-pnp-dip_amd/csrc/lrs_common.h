@@ -19,6 +19,60 @@ __device__ __forceinline__ floatx4 mfma16x16x4(float a, float b, floatx4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// ---- 64-bit lane moves and the two fp64 wave sums --------------------------------------------------
+// 64-bit value of register v in lane l (l uniform): two v_readlane_b32
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const int lo = __builtin_amdgcn_readlane((int)(unsigned)b, l);
+    const int hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
+    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+// v of the lane CTRL names, for permutations in which every lane reads a lane of its own row
+// (quad_perm, row_mirror, row_half_mirror): no 'old' value is needed, so mov_dpp (bound_ctrl) instead
+// of update_dpp(0, ...) saves the zeroing of each destination
+template <int CTRL>
+__device__ __forceinline__ double dpp_perm_f64(double v) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_mov_dpp((int)(b & 0xffffffffLL), CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xF, 0xF, true);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+// v of the lane CTRL names, 0.0 where that lane is outside the row or the row is masked out
+// (row_shr, row_bcast with a row mask)
+template <int CTRL, int ROWMASK = 0xF>
+__device__ __forceinline__ double dpp_shift_f64(double v) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROWMASK, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROWMASK, 0xF, false);
+    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+// Two sums over the 64 lanes, each uniform over the wave and in a fixed order (deterministic).  They
+// add the lanes in DIFFERENT orders, so they round differently and are not interchangeable: results
+// that were recorded with one (the DIP engine's losses and norms, the SVT's eigensolver) keep it.
+//  butterfly: xor 1, xor 2, half-row mirror, row mirror -- every lane of a 16-lane row then holds the
+//             row's sum as a balanced tree -- then (row 0 + row 1) + (row 2 + row 3) by readlane
+__device__ __forceinline__ double wave_sum_butterfly(double v) {
+    v += dpp_perm_f64<0xB1>(v);    // quad_perm [1,0,3,2]
+    v += dpp_perm_f64<0x4E>(v);    // quad_perm [2,3,0,1]
+    v += dpp_perm_f64<0x141>(v);   // row_half_mirror
+    v += dpp_perm_f64<0x140>(v);   // row_mirror
+    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+//  scan: row_shr 1 / 2 / 4 / 8 prefix sums within each row, row_bcast 15 / 31 carry the row totals
+//        upwards, lane 63 holds the whole sum
+__device__ __forceinline__ double wave_sum_scan(double v) {
+    v += dpp_shift_f64<0x111>(v);
+    v += dpp_shift_f64<0x112>(v);
+    v += dpp_shift_f64<0x114>(v);
+    v += dpp_shift_f64<0x118>(v);
+    v += dpp_shift_f64<0x142, 0xA>(v);
+    v += dpp_shift_f64<0x143, 0xC>(v);
+    return readlane_f64(v, 63);
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per device: set it once per device a
 // kernel is launched on (bit d of `done` = device d done; devices >= 64 are set on every call).
 inline int lds_opt_in(const void *fn, int bytes, std::atomic<uint64_t> &done) {

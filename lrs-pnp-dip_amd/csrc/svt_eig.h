@@ -37,41 +37,13 @@ constexpr int kEigThreads = 1024;
 // packed upper-triangle index of (i <= j) in an n x n symmetric matrix
 __device__ __forceinline__ int pk_idx(int i, int j, int n) { return i * n - ((i * (i - 1)) >> 1) + (j - i); }
 
-template <int CTRL, int ROWMASK = 0xF>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROWMASK, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROWMASK, 0xF, false);
-    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-// 64-bit value of register v in lane l (l uniform)
-__device__ __forceinline__ double rl64(double v, int l) {
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const int lo = __builtin_amdgcn_readlane((int)(unsigned)b, l);
-    const int hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
-    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-// Sum over the 64 lanes, returned in every lane (bitwise the same in every wave for the same data:
-// fixed order row_shr 1/2/4/8 scans, then row_bcast 15/31, lane 63 broadcast).
-__device__ __forceinline__ double wave_sum_dpp(double v) {
-    v += dpp_f64<0x111>(v);
-    v += dpp_f64<0x112>(v);
-    v += dpp_f64<0x114>(v);
-    v += dpp_f64<0x118>(v);
-    v += dpp_f64<0x142, 0xA>(v);
-    v += dpp_f64<0x143, 0xC>(v);
-    return rl64(v, 63);
-}
-
 // element j (uniform) of a wave-distributed vector r[t] = x[lane + 64 t].  readlane reads the
 // source lane's register whatever the EXEC mask, so it must be applied to the registers every lane
 // loaded (r[t]) and the choice among them made afterwards: a vector select in front of it would
 // leave the inactive lanes' values unwritten.
 __device__ __forceinline__ double wdist(const double (&r)[4], int j) {
     const int t = j >> 6, l = j & 63;
-    const double v0 = rl64(r[0], l), v1 = rl64(r[1], l), v2 = rl64(r[2], l), v3 = rl64(r[3], l);
+    const double v0 = readlane_f64(r[0], l), v1 = readlane_f64(r[1], l), v2 = readlane_f64(r[2], l), v3 = readlane_f64(r[3], l);
     return t == 0 ? v0 : t == 1 ? v1 : t == 2 ? v2 : v3;
 }
 
@@ -102,7 +74,7 @@ __device__ __noinline__ void eig_tridiag(double *A, double *pv, double *shb, int
                 xv[t] = (j < n) ? A[rk + j - k] : 0.0;
                 sig = __fma_rn(xv[t], xv[t], sig);
             }
-            sig = wave_sum_dpp(sig);
+            sig = wave_sum_scan(sig);
             const double x0 = A[rk + 1];
             double beta = 0.0, e = x0;
             if (sig > 0.0) {
@@ -167,7 +139,7 @@ __device__ __noinline__ void eig_tridiag(double *A, double *pv, double *shb, int
             wj[t] = (j < n) ? pj : 0.0;
             kp = __fma_rn(wj[t], vj[t], kp);
         }
-        const double K = 0.5 * beta * wave_sum_dpp(kp);
+        const double K = 0.5 * beta * wave_sum_scan(kp);
 #pragma unroll
         for (int t = 0; t < 4; ++t) wj[t] = wj[t] - K * vj[t];
         // A_sub -= v w^T + w v^T on the upper triangle: wave per row, lanes over absolute j
@@ -257,7 +229,7 @@ __device__ __noinline__ void eig_values(const double *A, int n, double gl, doubl
             const int jn = min(64, n - 64 * t);
 #pragma unroll 4
             for (int l = 0; l < jn; ++l) {
-                const double d = rl64(dr[t], l), e2 = rl64(er[t], l);
+                const double d = readlane_f64(dr[t], l), e2 = readlane_f64(er[t], l);
                 sturm_step(d, e2, x1, pivmin, p1, pm1, c1);
                 sturm_step(d, e2, x2, pivmin, p2, pm2, c2);
                 if ((l & 3) == 3) {
@@ -429,7 +401,7 @@ __device__ __noinline__ void eig_backtransform(const double *A, const double *bl
                 double acc = 0.0;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) acc = __fma_rn(v[t], x[c][t], acc);
-                s[c] = wave_sum_dpp(acc);
+                s[c] = wave_sum_scan(acc);
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {

@@ -30,13 +30,13 @@ __device__ __forceinline__ void ab_store_b(S3Tile &T, const float (&v)[16]) {
         const int row = s3_row<false>(), c0 = s3_kb<false>() >> 3;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            s3bf8 p;
+            bf16x8 p;
 #pragma unroll
             for (int e = 0; e < 8; ++e) p[e] = __builtin_bit_cast(__bf16, (unsigned short)(__builtin_bit_cast(uint32_t, v[8 * h + e]) >> 16));
             const int ch = s3_chunk(row, c0 + h) * 8;
-            *reinterpret_cast<s3bf8 *>(&T.v[0][row][ch]) = p;
-            *reinterpret_cast<s3bf8 *>(&T.v[1][row][ch]) = p;
-            *reinterpret_cast<s3bf8 *>(&T.v[2][row][ch]) = p;
+            *reinterpret_cast<bf16x8 *>(&T.v[0][row][ch]) = p;
+            *reinterpret_cast<bf16x8 *>(&T.v[1][row][ch]) = p;
+            *reinterpret_cast<bf16x8 *>(&T.v[2][row][ch]) = p;
         }
     } else {
         s3_store<false>(T, v);
@@ -64,23 +64,23 @@ __global__ __launch_bounds__(256, 2) void k_ablate(GemmArgs g, LdPre la, LdFwdTM
     __builtin_amdgcn_sched_barrier(0);
     lb.setup(n0, tab, 0);
     __syncthreads();
-    s3f4 acc[4][4];
+    floatx4 acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = s3f4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     float vb[16], vb1[16];
     auto mma = [&]() {
         if constexpr (DBG & 4) return;
-        s3bf8 fb[4][3];
+        bf16x8 fb[4][3];
 #pragma unroll
         for (int b = 0; b < 4; ++b) s3_frag(Bs, wn + 16 * b + jl, gk, fb[b]);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            s3bf8 fa[3];
+            bf16x8 fa[3];
             s3_frag(As, wm + 16 * a + jl, gk, fa);
 #pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = s3_mfma6(fa, fb[b], acc[a][b]);
+            for (int b = 0; b < 4; ++b) acc[a][b] = split_mfma6(fa, fb[b], acc[a][b]);
         }
     };
     auto st = [&](const float (&b)[16]) {

@@ -41,11 +41,11 @@ __global__ __launch_bounds__(512, 1) void k_pc(GemmArgs g, LdPre la, LdFwdTM lb,
     const int wm = (wv >> 1) * 64, wn = (wv & 1) * 64;
     const int jl = lane & 15, gk = lane >> 4;
     uint64_t work = 0, wait = 0, t_last, ph[4] = {0, 0, 0, 0};
-    s3f4 acc[4][4];
+    floatx4 acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = s3f4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     RegP pa;
     float vb0[16], vb1[16];
     la.setup(m0, sm.tab, 0);
@@ -84,15 +84,15 @@ __global__ __launch_bounds__(512, 1) void k_pc(GemmArgs g, LdPre la, LdFwdTM lb,
             __builtin_amdgcn_s_waitcnt(0xc07f);
             ph[3] += __builtin_amdgcn_s_memtime() - tc;
         } else if (k0 < kend) {
-            s3bf8 fb[4][3];
+            bf16x8 fb[4][3];
 #pragma unroll
             for (int bb = 0; bb < 4; ++bb) s3_frag(sm.b[cur], wn + 16 * bb + jl, gk, fb[bb]);
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
-                s3bf8 fa[3];
+                bf16x8 fa[3];
                 s3_frag(sm.a[cur], wm + 16 * a + jl, gk, fa);
 #pragma unroll
-                for (int bb = 0; bb < 4; ++bb) acc[a][bb] = s3_mfma6(fa, fb[bb], acc[a][bb]);
+                for (int bb = 0; bb < 4; ++bb) acc[a][bb] = split_mfma6(fa, fb[bb], acc[a][bb]);
             }
             // the MFMA results: the wave's work ends when its last MFMA retires
             float s = acc[3][3][3];

@@ -58,23 +58,23 @@ __global__ __launch_bounds__(256, 2) void k_gemm_s3_phase(GemmArgs g, LA la, LB 
     lb.setup(n0, tab, 0);
     __syncthreads();
     STAMP(kSetup);
-    s3f4 acc[4][4];
+    floatx4 acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = s3f4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     float vb[16], vb1[16];
     RegP pa;
     auto mma = [&]() {
-        s3bf8 fb[4][3];
+        bf16x8 fb[4][3];
 #pragma unroll
         for (int b = 0; b < 4; ++b) s3_frag(Bs, wn + 16 * b + jl, gk, fb[b]);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            s3bf8 fa[3];
+            bf16x8 fa[3];
             s3_frag(As, wm + 16 * a + jl, gk, fa);
 #pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = s3_mfma6(fa, fb[b], acc[a][b]);
+            for (int b = 0; b < 4; ++b) acc[a][b] = split_mfma6(fa, fb[b], acc[a][b]);
         }
     };
     auto st = [&](const float (&b)[16]) {

@@ -89,21 +89,21 @@ __global__ __launch_bounds__(256, 2) void k_presplit(GemmArgs g, LdPre la, LdFwd
     __builtin_amdgcn_sched_barrier(0);
     lb.setup(n0, tab, 0);
     __syncthreads();
-    s3f4 acc[4][4];
+    floatx4 acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = s3f4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     auto mma = [&]() {
-        s3bf8 fb[4][3];
+        bf16x8 fb[4][3];
 #pragma unroll
         for (int b = 0; b < 4; ++b) s3_frag(Bs, wn + 16 * b + jl, gk, fb[b]);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            s3bf8 fa[3];
+            bf16x8 fa[3];
             s3_frag(As, wm + 16 * a + jl, gk, fa);
 #pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = s3_mfma6(fa, fb[b], acc[a][b]);
+            for (int b = 0; b < 4; ++b) acc[a][b] = split_mfma6(fa, fb[b], acc[a][b]);
         }
     };
     __builtin_amdgcn_sched_barrier(0);
@@ -132,12 +132,12 @@ __global__ __launch_bounds__(256, 2) void k_presplit(GemmArgs g, LdPre la, LdFwd
         }
 }
 
-// x [C][Ps] fp32 -> [3][Ps][Cp] bf16 planes (s3_split), channels >= C zero
+// x [C][Ps] fp32 -> [3][Ps][Cp] bf16 planes (split_bf16), channels >= C zero
 __global__ void k_planes(const float *x, int C, int Ps, int Cp, __bf16 *out) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= (int64_t)Ps * Cp) return;
     const int p = (int)(i / Cp), c = (int)(i - (int64_t)p * Cp);
-    const S3Split q = s3_split(c < C ? x[(int64_t)c * Ps + p] : 0.0f);
+    const Bf16Split q = split_bf16(c < C ? x[(int64_t)c * Ps + p] : 0.0f);
     out[i] = q.b0;
     out[(int64_t)Ps * Cp + i] = q.b1;
     out[2 * (int64_t)Ps * Cp + i] = q.b2;
