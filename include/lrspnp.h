@@ -228,14 +228,23 @@ typedef struct {
  * the eigensolver holds the packed fp64 Gram in its CU's LDS, above it (the 224-band cubes) the
  * same one-workgroup chain works on the packed Gram in ws (L2-resident), up to 256 bands.
  * Wide cubes, 256 < B <= lrs_svt_max_bands() = 512: the Gram and U = Z (I - E) are tiled over
- * column panels, and the eigen stage is always the one-workgroup Jacobi chain, whatever the
+ * column panels, and the eigen stage is by default the one-workgroup Jacobi chain, whatever the
  * LRS_SVT_JACOBI bit says (the state word reports path 3).  LRS_SVT_WARM alone enables its warm
  * start there: _gram then forms the warm-start products V^T (G V).  LRS_SVT_MULTI_WG with
  * B > 256 is LRS_E_UNSUPPORTED, as is any B above 512 (main_LRS_PnP.py:112-124's np.linalg.svd
- * takes any B).  The workspace grows with the rotation log: 131 MB at (P, B) = (40000, 512). */
+ * takes any B).  The workspace grows with the rotation log: 131 MB at (P, B) = (40000, 512).
+ *   LRS_SVT_WIDE_TRI (256 < B <= 512; ignored below, where the calls launch what they launch
+ *     without it): the tridiagonal solver instead of the Jacobi chain: a one-workgroup Householder
+ *     reduction, then eigenvalues, inverse iteration and back-transformation over many workgroups
+ *     and the certificate as fp64 matrix-core GEMMs, falling back to the Jacobi solve of the same
+ *     Gram when the certificate fails.  State path 4 (certified) or 5 (fallback).  It needs no
+ *     warm start (with LRS_SVT_WARM, _gram skips the products) and leaves its eigenvectors for a
+ *     later warm Jacobi call on the same ws.  LRS_SVT_JACOBI set as well: the Jacobi chain.  The
+ *     workspace is the same size. */
 #define LRS_SVT_WARM 1
 #define LRS_SVT_JACOBI 2
 #define LRS_SVT_MULTI_WG 4
+#define LRS_SVT_WIDE_TRI 8
 /* The largest band count the SVT calls accept (host-only): 512. */
 int64_t lrs_svt_max_bands(void);
 size_t lrs_svt_workspace(int64_t P, int64_t B);

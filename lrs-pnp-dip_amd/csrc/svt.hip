@@ -16,11 +16,12 @@
 //      << 1e-6 relative in U.
 // The whole chain runs on its own stream beside the sparse-coding kernel.
 // Wide cubes (256 < B <= 512, svt_wide.h): 1 and 5 are tiled over column panels, and 2-4 run on the
-// packed triangle in the workspace whatever solver the caller asked for.
+// packed triangle in the workspace whatever solver the caller asked for, unless LRS_SVT_WIDE_TRI asks
+// for 3' over many workgroups with its certificate as GEMMs on the fp64 matrix cores (svt_wide_eig.h).
 //
 // The stages: svt_gram.h (1, 2), svt_jacobi.h (3, 4), svt_eig.h (3'), svt_apply.h (5), svt_wide.h (the
-// wide Gram); svt_ws.h has the workspace and the table of which form serves which band count.  Here:
-// the launchers and the C entry points.
+// wide Gram), svt_wide_eig.h (the wide 3'); svt_ws.h has the workspace and the table of which form
+// serves which band count.  Here: the launchers and the C entry points.
 #include <algorithm>
 
 #include "lrs_common.h"
@@ -29,6 +30,7 @@
 #include "svt_gram.h"
 #include "svt_jacobi.h"
 #include "svt_wide.h"
+#include "svt_wide_eig.h"
 #include "svt_ws.h"
 
 using namespace lrs;
@@ -79,6 +81,13 @@ static int svt_shape_check(int64_t B, int warm) {
     return LRS_OK;
 }
 
+// The flag word as the launchers read it: LRS_SVT_WIDE_TRI means something above kMaxBp only.
+static int svt_flags(int64_t B, int warm) { return svt_shape(B).wide ? warm : warm & ~LRS_SVT_WIDE_TRI; }
+// The wide tridiagonal chain (svt_wide_eig.h) serves; an explicit LRS_SVT_JACOBI wins.
+static bool svt_wide_tri(int64_t B, int warm) {
+    return svt_shape(B).wide && (warm & LRS_SVT_WIDE_TRI) && !(warm & LRS_SVT_JACOBI);
+}
+
 extern "C" int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, int64_t *ld) {
     if (P <= 0 || B <= 0 || !offset_bytes || !ld) return LRS_E_INVALID;
     if (B + (B & 1) > kMaxBp) return LRS_E_UNSUPPORTED;
@@ -95,7 +104,9 @@ extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64
     if (ws_bytes < svt_ws_offsets(B).total) return LRS_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     SvtWs w = svt_ws_layout(ws, B);
-    if (!warm) {
+    const bool wide_tri = svt_wide_tri(B, warm);
+    warm = svt_flags(B, warm);
+    if (!warm || (wide_tri && !(warm & LRS_SVT_WARM))) {
         hipError_t e = hipMemsetAsync(w.state, 0, sizeof(int) * 4, st);
         if (e != hipSuccess) return (int)e;
     }
@@ -116,7 +127,7 @@ extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64
     hipLaunchKernelGGL(k_gram_reduce16, dim3((unsigned)((Bp * Bp + 255) / 256)), dim3(256), 0, st, w.partial, nslab,
                        sh.gram_nt, (int)B, Bp, w.G);
     LRS_CHECK_LAUNCH();
-    if ((warm & LRS_SVT_WARM) && ((warm & LRS_SVT_JACOBI) || sh.wide)) {
+    if ((warm & LRS_SVT_WARM) && ((warm & LRS_SVT_JACOBI) || sh.wide) && !wide_tri) {
         // A0 = V^T (G V) with the current V (unused when V is not valid yet: Jacobi starts from G)
         const dim3 g16((Bp + 15) / 16, (Bp + 15) / 16);
         hipLaunchKernelGGL(k_gemm_f64_state, g16, dim3(256), 0, st, w, 0);
@@ -155,7 +166,45 @@ extern "C" int lrs_svt_finish_f32(const float *X, const float *L2, float c2, int
     };
     const size_t smem = jacobi_lds(Bp, sh.ga);
     const size_t vsmem = vrebuild_lds(Bp);
-    if (sh.wide || (warm & LRS_SVT_JACOBI)) {   // wide: the Jacobi chain whatever the flag word asks for
+    const bool wide_tri = svt_wide_tri(B, warm);
+    warm = svt_flags(B, warm);
+    if (wide_tri) {
+        // tridiagonalisation, eigenvalues, inverse iteration, back-transformation; S = V^T V and its
+        // certificate, kWtMaxNs gated Newton-Schulz steps, the gated Jacobi fallback; then E as below
+        hipError_t ea = opt_in((const void *)k_svt_eig_wide_fb_vrebuild, vsmem);
+        if (ea != hipSuccess) return (int)ea;
+        const dim3 g64((unsigned)((Bp + 63) / 64), (unsigned)((Bp + 63) / 64));
+        hipLaunchKernelGGL(k_svt_eig_wide_tri, dim3(1), dim3(kEigThreads), sizeof(double) * Bp, st, w);
+        LRS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_svt_eig_wide_vals, dim3((unsigned)((4 * Bp + kEigMwThreads - 1) / kEigMwThreads)),
+                           dim3(kEigMwThreads), 0, st, w);
+        LRS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_svt_eig_wide_vecs, dim3((unsigned)((Bp + kEigMwThreads - 1) / kEigMwThreads)),
+                           dim3(kEigMwThreads), 0, st, w);
+        LRS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_svt_eig_wide_back, dim3((unsigned)((Bp + 15) / 16)), dim3(256), 0, st, w);
+        LRS_CHECK_LAUNCH();
+        for (int step = 0; step <= kWtMaxNs; ++step) {
+            if (step > 0) {
+                hipLaunchKernelGGL(k_svt_eig_wide_gemm<true>, g64, dim3(256), 0, st, w, step);
+                LRS_CHECK_LAUNCH();
+            }
+            hipLaunchKernelGGL(k_svt_eig_wide_gemm<false>, g64, dim3(256), 0, st, w, step);
+            LRS_CHECK_LAUNCH();
+            hipLaunchKernelGGL(k_svt_eig_wide_cert, dim3(1), dim3(kEigThreads), 0, st, w, step);
+            LRS_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(k_svt_eig_wide_fb_jacobi, dim3(1), dim3(kJacobiThreads), smem, st, w);
+        LRS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_svt_eig_wide_fb_vrebuild, dim3((unsigned)((Bp + sh.vrows - 1) / sh.vrows)), dim3(1024),
+                           vsmem, st, w);
+        LRS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_svt_eig_wide_fb_state, dim3(1), dim3(1), 0, st, w);
+        LRS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_build_E, dim3((unsigned)((B + 15) / 16), (unsigned)((B + 15) / 16)), dim3(256), 0, st,
+                           w, (int)B, tau);
+        LRS_CHECK_LAUNCH();
+    } else if (sh.wide || (warm & LRS_SVT_JACOBI)) {   // wide: the Jacobi chain unless LRS_SVT_WIDE_TRI asks
         const int jwarm = warm & LRS_SVT_WARM;
         hipError_t ea = opt_in((const void *)k.jacobi, smem);
         if (ea == hipSuccess) ea = opt_in((const void *)k_jacobi_vrebuild, vsmem);
@@ -214,7 +263,9 @@ extern "C" int lrs_svt_f32(const float *X, const float *L2, float c2, int64_t P,
 }
 
 // Diagnostics (not in include/lrspnp.h): state words of the last call (host copy): V valid, V buffer,
-// Jacobi rounds, sweeps, path (1 tridiagonal, 2 Jacobi fallback, 3 Jacobi); words 5-31 are spare.
+// Jacobi rounds, sweeps, path (1 tridiagonal, 2 Jacobi fallback, 3 Jacobi, 4 wide tridiagonal, 5 its
+// Jacobi fallback), Newton-Schulz steps and certificate flag of the wide tridiagonal chain; words 7-31
+// are spare.
 extern "C" int lrs_diag_svt_state(void *ws, int64_t P, int64_t B, int *out32) {
     if (!ws || !out32 || P <= 0 || B <= 0) return LRS_E_INVALID;
     if (svt_shape_check(B, 0) != LRS_OK) return LRS_E_UNSUPPORTED;

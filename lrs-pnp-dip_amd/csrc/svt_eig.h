@@ -21,6 +21,8 @@
 // while the sparse-coding kernel holds the rest of the chip.  The phases are separate
 // (non-inlined) functions so each gets its own register allocation.  k_svt_eig is that workgroup;
 // the k_svt_eig_* kernels at the end run the same device functions over several (LRS_SVT_MULTI_WG).
+// Phases A, B, C and E take the registers of a wave-distributed vector as a template parameter (NV = 4:
+// 256 columns, every kernel here; NV = 8: the wide cubes' chain, svt_wide_eig.h).
 #pragma once
 
 #include <float.h>
@@ -46,6 +48,17 @@ __device__ __forceinline__ double wdist(const double (&r)[4], int j) {
     const double v0 = readlane_f64(r[0], l), v1 = readlane_f64(r[1], l), v2 = readlane_f64(r[2], l), v3 = readlane_f64(r[3], l);
     return t == 0 ? v0 : t == 1 ? v1 : t == 2 ? v2 : v3;
 }
+// the same over 8 registers (wide cubes, svt_wide_eig.h): x[lane + 64 t], t < 8
+__device__ __forceinline__ double wdist(const double (&r)[8], int j) {
+    const int t = j >> 6, l = j & 63;
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = readlane_f64(r[u], l);
+    double x = v[7];
+#pragma unroll
+    for (int u = 6; u >= 0; --u) x = t == u ? v[u] : x;
+    return x;
+}
 
 // Workgroup barrier of the chain: LDS-only while the packed A is in LDS (B <= kLdsMaxBp), a full
 // one (global stores drained and visible to the workgroup) when A lives in the workspace.
@@ -55,21 +68,54 @@ __device__ __forceinline__ void eig_bar() {
     else lds_barrier();
 }
 
+// p_i = beta * (A_sub v)_i of column k's reflector for a row i past the 256 that eig_tridiag's own
+// pass covers (n > 256 only): that pass's statements, four threads per row.  A function of its own so
+// that the pass below stays the code it is at NV = 4 (a shared helper changes its schedule).
+__device__ __forceinline__ void eig_matvec_row(const double *A, double *pv, int n, int k, int i, double beta) {
+    const int q = threadIdx.x & 3, rk = pk_idx(k, k, n);
+    double acc = 0.0;
+    if (i < n) {
+        const int ri = pk_idx(i, i, n) - i;   // A(i, j) = A[ri + j], j >= i
+        for (int j0 = k + 1 + q; j0 < n; j0 += 32) {
+            double av[8], vv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int j = j0 + 4 * u;
+                const int jc = (j < n) ? j : n - 1;
+                const int aa = (jc >= i) ? ri + jc : pk_idx(jc, i, n);
+                av[u] = A[aa];
+                vv[u] = A[rk + jc - k];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int j = j0 + 4 * u;
+                const double vj = (j == k + 1) ? 1.0 : vv[u];
+                if (j < n) acc = __fma_rn(av[u], vj, acc);
+            }
+        }
+    }
+    acc += __shfl_xor(acc, 1, 64);
+    acc += __shfl_xor(acc, 2, 64);
+    if (i < n && q == 0) pv[i] = beta * acc;
+}
+
 // ---- A. tridiagonalisation: A (packed) -> T on its diagonal / first superdiagonal ---------------
 // Per column k: wave 0 forms the reflector; the matvec p = beta A_sub v runs four threads per row
 // with eight loads in flight per thread; the rank-2 update runs one wave per row over absolute
 // column lanes (v_j, w_j computed once per lane), two rows per batch.  GA: A is in global memory
 // (the workspace, L2-resident: B > kLdsMaxBp, whose packed triangle exceeds the 160 KiB of LDS).
-template <bool GA>
+// NV: registers of a wave-distributed row (n <= 64 NV: 4 up to 256 columns, 8 for the wide cubes,
+// whose matvec then takes two passes of 256 rows); the same template parameter widens the phases below.
+template <bool GA, int NV = 4>
 __device__ __noinline__ void eig_tridiag(double *A, double *pv, double *shb, int n, double *beta_g) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     constexpr int NW = kEigThreads / 64;
     for (int k = 0; k < n - 2; ++k) {
         const int rk = pk_idx(k, k, n);   // A(k, j) = A[rk + j - k]
         if (wv == 0) {
-            double xv[4], sig = 0.0;
+            double xv[NV], sig = 0.0;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
+            for (int t = 0; t < NV; ++t) {
                 const int j = k + 2 + lane + 64 * t;
                 xv[t] = (j < n) ? A[rk + j - k] : 0.0;
                 sig = __fma_rn(xv[t], xv[t], sig);
@@ -85,7 +131,7 @@ __device__ __noinline__ void eig_tridiag(double *A, double *pv, double *shb, int
                 e = mu;
                 const double r = 1.0 / v1;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
+                for (int t = 0; t < NV; ++t) {
                     const int j = k + 2 + lane + 64 * t;
                     if (j < n) A[rk + j - k] = xv[t] * r;
                 }
@@ -127,11 +173,12 @@ __device__ __noinline__ void eig_tridiag(double *A, double *pv, double *shb, int
             acc += __shfl_xor(acc, 2, 64);
             if (i < n && q == 0) pv[i] = beta * acc;
         }
+        if constexpr (NV > 4) eig_matvec_row(A, pv, n, k, k + 1 + (tid >> 2) + kEigThreads / 4, beta);
         eig_bar<GA>();
         // K = beta/2 p.v (every wave computes the same value), w = p - K v
-        double vj[4], wj[4], kp = 0.0;
+        double vj[NV], wj[NV], kp = 0.0;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        for (int t = 0; t < NV; ++t) {
             const int j = k + 1 + lane + 64 * t;
             const int jc = (j < n) ? j : n - 1;
             const double a = A[rk + jc - k], pj = pv[jc];
@@ -141,13 +188,15 @@ __device__ __noinline__ void eig_tridiag(double *A, double *pv, double *shb, int
         }
         const double K = 0.5 * beta * wave_sum_scan(kp);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) wj[t] = wj[t] - K * vj[t];
-        // A_sub -= v w^T + w v^T on the upper triangle: wave per row, lanes over absolute j
-        for (int i0 = k + 1 + wv; i0 < n; i0 += 2 * NW) {
-            double a[2][4], vi[2], wi[2];
-            int ri[2];
+        for (int t = 0; t < NV; ++t) wj[t] = wj[t] - K * vj[t];
+        // A_sub -= v w^T + w v^T on the upper triangle: wave per row, lanes over absolute j; NR rows per
+        // batch (one at NV = 8: two rows of 8 registers would spill)
+        constexpr int NR = NV > 4 ? 1 : 2;
+        for (int i0 = k + 1 + wv; i0 < n; i0 += NR * NW) {
+            double a[NR][NV], vi[NR], wi[NR];
+            int ri[NR];
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
+            for (int r = 0; r < NR; ++r) {
                 const int i = i0 + r * NW;
                 const int ic = (i < n) ? i : n - 1;
                 ri[r] = pk_idx(ic, ic, n) - ic;
@@ -155,16 +204,16 @@ __device__ __noinline__ void eig_tridiag(double *A, double *pv, double *shb, int
                 vi[r] = (ic == k + 1) ? 1.0 : vr;
                 wi[r] = pv[ic] - K * vi[r];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
+                for (int t = 0; t < NV; ++t) {
                     const int j = k + 1 + lane + 64 * t;
                     a[r][t] = (i < n && j >= i && j < n) ? A[ri[r] + j] : 0.0;
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
+            for (int r = 0; r < NR; ++r) {
                 const int i = i0 + r * NW;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
+                for (int t = 0; t < NV; ++t) {
                     const int j = k + 1 + lane + 64 * t;
                     if (i < n && j >= i && j < n) A[ri[r] + j] = a[r][t] - (vi[r] * wj[t] + wi[r] * vj[t]);
                 }
@@ -201,12 +250,13 @@ __device__ __forceinline__ void sturm_rescale(double &p, double &pm) {
 // d_j and e_{j-1}^2 live in registers distributed over the lanes of every wave and reach the
 // Sturm chains by readlane (no memory access inside the sequence).  The number of sign changes
 // of p_0 = 1, p_1(x), ..., p_n(x) is the number of eigenvalues below x.
+template <int NV = 4>
 __device__ __noinline__ void eig_values(const double *A, int n, double gl, double gu, double tn, double pivmin,
                                         double *lamv, double *lam_g, int tid0 = 0) {
     const int tid = tid0 + (int)threadIdx.x, lane = tid & 63;   // tid0: this workgroup's first thread (multi-WG)
-    double dr[4], er[4];
+    double dr[NV], er[NV];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < NV; ++t) {
         const int j = lane + 64 * t;
         dr[t] = (j < n) ? A[pk_idx(j, j, n)] : 0.0;
         const double e = (j >= 1 && j < n) ? A[pk_idx(j - 1, j - 1, n) + 1] : 0.0;
@@ -225,7 +275,7 @@ __device__ __noinline__ void eig_values(const double *A, int n, double gl, doubl
         double p1 = 1.0, pm1 = 0.0, p2 = 1.0, pm2 = 0.0;
         int c1 = 0, c2 = 0;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        for (int t = 0; t < NV; ++t) {
             const int jn = min(64, n - 64 * t);
 #pragma unroll 4
             for (int l = 0; l < jn; ++l) {
@@ -265,12 +315,13 @@ __device__ __noinline__ void eig_values(const double *A, int n, double gl, doubl
 // W[j * n + i] = component j of eigenvector i (coalesced across threads).  d_j, e_j by readlane;
 // global loads issued kEigUnroll rows ahead.  Returns ||T w_i - lambda_i w_i|| (0 for i >= n).
 constexpr int kEigUnroll = 4;
+template <int NV = 4>
 __device__ __noinline__ double eig_vectors(const double *A, const double *lamv, int n, double tn, double *F,
                                            double *W, int tid0 = 0) {
     const int i = tid0 + (int)threadIdx.x, lane = i & 63;
-    double dr[4], er[4];   // d_j, e_j = A(j, j+1)
+    double dr[NV], er[NV];   // d_j, e_j = A(j, j+1)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < NV; ++t) {
         const int j = lane + 64 * t;
         const int idx = (j < n) ? pk_idx(j, j, n) : 0;
         dr[t] = (j < n) ? A[idx] : 0.0;
@@ -371,15 +422,16 @@ __device__ __noinline__ double eig_vectors(const double *A, const double *lamv, 
 
 // ---- E. V = H_0 H_1 ... H_{n-3} W (V[j * n + c] = component j of eigenvector c) ----------------
 // beta_k from LDS (bl), reflector k from row k of the packed A.
+template <int NV = 4>
 __device__ __noinline__ void eig_backtransform(const double *A, const double *bl, int n, const double *W,
                                                double *V, int wave0 = 0, int nwaves = kEigThreads / 64) {
     const int lane = threadIdx.x & 63, wv = wave0 + (int)(threadIdx.x >> 6);   // wave0 / nwaves: multi-WG
     for (int c0 = 4 * wv; c0 < n; c0 += 4 * nwaves) {
-        double x[4][4];
+        double x[4][NV];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
+            for (int t = 0; t < NV; ++t) {
                 const int j = lane + 64 * t;
                 x[c][t] = (j < n && c0 + c < n) ? W[(int64_t)j * n + c0 + c] : 0.0;
             }
@@ -387,9 +439,9 @@ __device__ __noinline__ void eig_backtransform(const double *A, const double *bl
             const double beta = bl[k];
             if (beta == 0.0) continue;
             const int rk = pk_idx(k, k, n);
-            double v[4];
+            double v[NV];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
+            for (int t = 0; t < NV; ++t) {
                 const int j = lane + 64 * t;
                 const int jc = (j > k + 1 && j < n) ? j : k + 1;
                 const double a = A[rk + jc - k];
@@ -400,20 +452,20 @@ __device__ __noinline__ void eig_backtransform(const double *A, const double *bl
             for (int c = 0; c < 4; ++c) {
                 double acc = 0.0;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) acc = __fma_rn(v[t], x[c][t], acc);
+                for (int t = 0; t < NV; ++t) acc = __fma_rn(v[t], x[c][t], acc);
                 s[c] = wave_sum_scan(acc);
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const double bsc = beta * s[c];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) x[c][t] = x[c][t] - bsc * v[t];
+                for (int t = 0; t < NV; ++t) x[c][t] = x[c][t] - bsc * v[t];
             }
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
+            for (int t = 0; t < NV; ++t) {
                 const int j = lane + 64 * t;
                 if (j < n && c0 + c < n) V[(int64_t)j * n + c0 + c] = x[c][t];
             }

@@ -27,7 +27,7 @@ __host__ __device__ constexpr int gram_npairs(int nt) { return nt * (nt + 1) / 2
 // The launched forms per band count B (Bp = B rounded up to even).  Every launch site, LDS size and
 // workspace extent that depends on the band count reads it here.
 struct SvtShape {
-    bool wide;      // k_gram_wide, the Jacobi chain whatever solver is asked for, the apply over column panels
+    bool wide;      // k_gram_wide, the Jacobi chain (or, LRS_SVT_WIDE_TRI, svt_wide_eig.h's), the apply over column panels
     bool ga;        // the solvers' packed triangle in the workspace (global A), not in LDS
     int gram_nt;    // 16-column blocks of the Gram partials; B <= kMaxBp: k_gram_mfma<gram_nt, gram_nw>
     int gram_nw;    //   its waves per workgroup
@@ -63,16 +63,22 @@ struct SvtWs {
     double *lam;      // [Bp]      eigenvalues (diag of the converged A)
     double *rot;      // [kMaxSweeps*(Bp-1)][Bp/2][2]  (c, s) per round and pair (84 MB at Bp = 512)
     double *beta;     // [Bp]      Householder scalars (tridiagonal path)
-    double *F;        // [Bp][4][Bp] pivoted LU rows of T - lambda_i I (inverse iteration; none when wide)
+    double *F;        // [Bp][4][Bp] pivoted LU rows of T - lambda_i I (inverse iteration; wide: the head of rot)
     float *E;         // [B][B]
     float *Fp;        // [fp_steps][B][4]  I - E in the apply kernels' fragment order
     int *state;       // [0] V valid, [1] current V buffer, [2] rounds, [3] sweeps,
-                      // [4] path of the last solve (1 tridiagonal, 2 Jacobi fallback, 3 Jacobi)
+                      // [4] path of the last solve (1 tridiagonal, 2 Jacobi fallback, 3 Jacobi, 4 wide
+                      // tridiagonal, 5 its Jacobi fallback), [5] Newton-Schulz steps and [6] certificate
+                      // flag of the wide tridiagonal chain (svt_wide_eig.h)
     int64_t Bp;
 };
 
 // Byte offsets of the arrays above from the workspace base (each 256-aligned), in this order, and
 // the size to allocate.  They depend on the band count alone.
+// Wide cubes have no F region of their own: their tridiagonal chain's F (4 Bp^2 doubles: 2.1 MB at
+// Bp = 258, 8.4 MB at 512) is the head of rot (kMaxSweeps (Bp - 1) (Bp / 2) 16 B: 21 MB and 84 MB).
+// F is written and read by the inverse iteration alone and is dead before the chain's Jacobi
+// fallback, the only writer of the rotation log in that call, starts.
 struct SvtWsOffsets {
     size_t state, partial, G, A0, T, V[2], lam, rot, beta, F, Fp, E, total;
 };
@@ -99,7 +105,7 @@ inline SvtWsOffsets svt_ws_offsets(int64_t B) {
     o.lam = take(Bp * sizeof(double));
     o.rot = take((size_t)kMaxSweeps * (Bp - 1) * (Bp / 2) * 2 * sizeof(double));
     o.beta = take(Bp * sizeof(double));
-    o.F = take(sh.wide ? 0 : 4 * mat);
+    o.F = sh.wide ? o.rot : take(4 * mat);
     o.Fp = take((size_t)sh.fp_steps * B * 4 * sizeof(float));
     o.E = p;
     o.total = o.E + (size_t)B * B * sizeof(float) + 256;

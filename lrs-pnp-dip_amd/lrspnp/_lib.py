@@ -31,6 +31,9 @@ DIP_F32, DIP_SPLIT_BF16 = 0, 1
 
 ISTA_ALGO_AUTO, ISTA_ALGO_GENERIC = 0, 1
 
+# flag word (`warm`) of the SVT calls
+SVT_WARM, SVT_JACOBI, SVT_MULTI_WG, SVT_WIDE_TRI = 1, 2, 4, 8
+
 
 class IstaOpts(ctypes.Structure):
     _fields_ = [("precision", ctypes.c_int32), ("max_workgroups", ctypes.c_int32), ("algorithm", ctypes.c_int32),

@@ -40,6 +40,9 @@ class LrsPnPConfig:
     # replicated solve is on the critical path; the one-workgroup chain beside a whole-cube sparse
     # coding (a multi-launch chain there waits for free CUs between its launches).
     svt_multi_wg: str = "auto"
+    # eigen stage of wide cubes (256 < B <= 512; ignored below): 'jacobi', the warm-started
+    # one-workgroup Jacobi chain, or 'tri', the tridiagonal chain over many workgroups (LRS_SVT_WIDE_TRI)
+    svt_wide_solver: str = "jacobi"
     lowrank: str = "svt"          # 'svt' (main_LRS_PnP.py:315) or 'dip' (…1-LiP.py:399-411)
     dip: object = None            # lrspnp.dip.DipConfig for lowrank='dip' (None: reference defaults)
     dip_seed: int = 0             # DIP init seed of outer iteration t is dip_seed + t
@@ -193,6 +196,9 @@ class LrsPnP:
             raise LrsError(f"unknown ista_dip_order {cfg.ista_dip_order!r} (beside | before)")
         if cfg.svt_multi_wg not in ("auto", "on", "off"):
             raise LrsError(f"unknown svt_multi_wg {cfg.svt_multi_wg!r} (auto | on | off)")
+        if cfg.svt_wide_solver not in ("jacobi", "tri"):
+            raise LrsError(f"unknown svt_wide_solver {cfg.svt_wide_solver!r} (jacobi | tri)")
+        self.svt_wide_tri = self.svt_wide and cfg.svt_wide_solver == "tri"
         if self.K <= 512 and (cfg.ista_patterns == "on" or (
                 cfg.ista_patterns == "auto" and ops.ista_pat_preferred(n, self.K, self.nb, self.npat, cfg.Nit))):
             plan, self.pat_ntiles = ops.ista_pat_plan(inv.reshape(-1), self.npat)
@@ -290,7 +296,7 @@ class LrsPnP:
     def low_rank(self, stream=None, s_out=None):
         warm = self.cfg.svt_warm and self.iteration > 0
         return ops.svt(self.X, self.L2, self.c2, self.tau, self.svt_ws, U=self.U, s_out=s_out, warm=warm,
-                       stream=stream, method=self.cfg.svt_method)
+                       stream=stream, method=self.cfg.svt_method, wide_tri=self.svt_wide_tri)
 
     def low_rank_dip(self, stream):
         """U = DIP(X + L2/mu2) (…1-LiP.py:399-411) on `stream`; the host polls early stopping."""
@@ -313,7 +319,8 @@ class LrsPnP:
         warm = self.cfg.svt_warm and self.iteration > 0
         stream_wait(lr, main)
         # low-rank prox, first half (whole chip, ~0.2 ms): fp64 Gram (+ Jacobi warm-start products)
-        ops.svt_gram(self.X, self.L2, self.c2, self.svt_ws, warm=warm, stream=lr, method=self.cfg.svt_method)
+        ops.svt_gram(self.X, self.L2, self.c2, self.svt_ws, warm=warm, stream=lr, method=self.cfg.svt_method,
+                     wide_tri=self.svt_wide_tri)
         if self.comm is not None:
             self.comm.allreduce_(self.gram, lr)       # the cube's Gram = sum of the slabs' Grams
         gram_done = lr.record_event()
@@ -322,7 +329,8 @@ class LrsPnP:
         if mw not in ("auto", "on", "off"):
             raise LrsError(f"unknown svt_multi_wg {mw!r} (auto | on | off)")
         ops.svt_finish(self.X, self.L2, self.c2, self.tau, self.svt_ws, self.U, warm=warm, stream=lr,
-                       method=self.cfg.svt_method, multi_wg=mw == "on" or (mw == "auto" and self.comm is not None))
+                       method=self.cfg.svt_method, multi_wg=mw == "on" or (mw == "auto" and self.comm is not None),
+                       wide_tri=self.svt_wide_tri)
         ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
                    stream=main)
         if self.cfg.svt_gram_first or self.cfg.svt_method == "jacobi" or self.svt_wide:

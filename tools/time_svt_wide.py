@@ -12,7 +12,9 @@ Per shape, median of --reps:
   apply       the apply kernel alone (lrs_diag_svt_apply)
   sweeps      Jacobi sweeps cold / warm (0 on the tridiagonal path)
 At B = 256 both solvers of the existing path are timed: 'tri' (the default there; no warm start) and
-'jacobi' (the chain the wide cubes run).
+'jacobi' (the chain the wide cubes run).  Every wide shape is timed with both of its eigen stages: the
+default Jacobi chain ('tri' row, path 3) and the tridiagonal chain of LRS_SVT_WIDE_TRI ('wide_tri' row,
+path 4; its "warm" column is the same cold chain on the perturbed matrix: it takes no warm start).
 """
 import argparse
 import json
@@ -47,7 +49,7 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
-def shape(P, B, method):
+def shape(P, B, method, wide_tri=False):
     rng = np.random.default_rng(P + B)
     Z = rng.random((P, 8)) @ rng.random((8, B)) * 0.3 + 0.02 * rng.standard_normal((P, B))
     X = torch.from_numpy(Z.astype(np.float32)).cuda()
@@ -55,23 +57,25 @@ def shape(P, B, method):
     L2 = torch.from_numpy((0.01 * rng.standard_normal((P, B))).astype(np.float32)).cuda()
     U = torch.empty_like(X)
     ws = ops.svt_workspace(P, B, "cuda")
-    ops.svt(X, L2, C2, TAU, ws, U=U, method=method)   # first launches (module load, LDS opt-in)
+    kw = {"method": method, "wide_tri": wide_tri}
+    ops.svt(X, L2, C2, TAU, ws, U=U, **kw)   # first launches (module load, LDS opt-in)
     torch.cuda.synchronize()
     t = {k: [] for k in ("gram", "gram_warm", "fin_cold", "fin_warm", "apply")}
     sweeps = [0, 0]
     warmable = method == "jacobi" or B > 256
     for _ in range(a.reps):
-        t["gram"].append(timed(lambda: ops.svt_gram(X, L2, C2, ws, method=method)))
-        t["fin_cold"].append(timed(lambda: ops.svt_finish(X, L2, C2, TAU, ws, U, method=method)))
+        t["gram"].append(timed(lambda: ops.svt_gram(X, L2, C2, ws, **kw)))
+        t["fin_cold"].append(timed(lambda: ops.svt_finish(X, L2, C2, TAU, ws, U, **kw)))
         state = ops.svt_state(ws, P, B)
-        path, sweeps[0] = state[4], state[3] if state[4] != 1 else 0
+        path, sweeps[0] = state[4], state[3] if state[4] not in (1, 4) else 0
         if warmable:
-            t["gram_warm"].append(timed(lambda: ops.svt_gram(X2, L2, C2, ws, warm=True, method=method)))
-            t["fin_warm"].append(timed(lambda: ops.svt_finish(X2, L2, C2, TAU, ws, U, warm=True, method=method)))
-            sweeps[1] = ops.svt_state(ws, P, B)[3]
+            t["gram_warm"].append(timed(lambda: ops.svt_gram(X2, L2, C2, ws, warm=True, **kw)))
+            t["fin_warm"].append(timed(lambda: ops.svt_finish(X2, L2, C2, TAU, ws, U, warm=True, **kw)))
+            state = ops.svt_state(ws, P, B)
+            sweeps[1] = state[3] if state[4] != 4 else 0
         t["apply"].append(timed(lambda: ops.svt_apply_only(X2, L2, C2, ws, U)))
     m = {k: float(np.median(v)) if v else None for k, v in t.items()}
-    return {"P": P, "B": B, "method": method, "path": path, "ws_MB": ws.numel() / 1e6,
+    return {"P": P, "B": B, "method": "wide_tri" if wide_tri else method, "path": path, "ws_MB": ws.numel() / 1e6,
             "gram_ms": m["gram"], "gram_warm_ms": m["gram_warm"],
             "eig_cold_ms": m["fin_cold"] - m["apply"],
             "eig_warm_ms": m["fin_warm"] - m["apply"] if warmable else None,
@@ -81,11 +85,12 @@ def shape(P, B, method):
 rows = [shape(a.P, 256, "tri"), shape(a.P, 256, "jacobi")]
 for B in (320, 448, 512):
     rows.append(shape(a.P, B, "tri"))
+    rows.append(shape(a.P, B, "tri", wide_tri=True))
 f = lambda v: "     -" if v is None else f"{v:6.0f}" if isinstance(v, int) else f"{v:9.3f}"
-print(f"{'P':>6} {'B':>4} {'solver':>7} {'path':>4} {'ws MB':>9} {'gram':>9} {'gram warm':>9} {'eig cold':>9} "
+print(f"{'P':>6} {'B':>4} {'solver':>8} {'path':>4} {'ws MB':>9} {'gram':>9} {'gram warm':>9} {'eig cold':>9} "
       f"{'eig warm':>9} {'apply':>9} {'sweeps c/w':>10}   (ms, median of {a.reps})")
 for r in rows:
-    print(f"{r['P']:6d} {r['B']:4d} {r['method']:>7} {r['path']:4d} {f(r['ws_MB'])} {f(r['gram_ms'])} "
+    print(f"{r['P']:6d} {r['B']:4d} {r['method']:>8} {r['path']:4d} {f(r['ws_MB'])} {f(r['gram_ms'])} "
           f"{f(r['gram_warm_ms'])} {f(r['eig_cold_ms'])} {f(r['eig_warm_ms'])} {f(r['apply_ms'])} "
           f"{r['sweeps_cold']:>5}/{'-' if r['sweeps_warm'] is None else r['sweeps_warm']}")
     print(json.dumps(r))
