@@ -240,11 +240,20 @@ typedef struct {
  *     Gram when the certificate fails.  State path 4 (certified) or 5 (fallback).  It needs no
  *     warm start (with LRS_SVT_WARM, _gram skips the products) and leaves its eigenvectors for a
  *     later warm Jacobi call on the same ws.  LRS_SVT_JACOBI set as well: the Jacobi chain.  The
- *     workspace is the same size. */
+ *     workspace is the same size.
+ *   LRS_SVT_WIDE_MW (with LRS_SVT_WIDE_TRI on 256 < B <= 512; ignored wherever that chain does not
+ *     serve: B <= 256, LRS_SVT_WIDE_TRI not set, or LRS_SVT_JACOBI set): that chain with its
+ *     Householder reduction spread over many workgroups as well, one launch per column of the Gram
+ *     (Bp launches on the caller's stream, the launch boundary the only synchronisation between
+ *     workgroups; fixed-order sums, so reruns are bit-identical); every later phase is the same.
+ *     _gram treats it as LRS_SVT_WIDE_TRI alone.  Diagnostic state word 7 is 1 after such a solve
+ *     and 0 after a solve of the one-workgroup reduction; the path is still 4 or 5.  The workspace
+ *     is the same size: the reduction's scratch aliases regions that are dead while it runs. */
 #define LRS_SVT_WARM 1
 #define LRS_SVT_JACOBI 2
 #define LRS_SVT_MULTI_WG 4
 #define LRS_SVT_WIDE_TRI 8
+#define LRS_SVT_WIDE_MW 16
 /* The largest band count the SVT calls accept (host-only): 512. */
 int64_t lrs_svt_max_bands(void);
 size_t lrs_svt_workspace(int64_t P, int64_t B);

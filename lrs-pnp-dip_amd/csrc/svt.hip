@@ -17,11 +17,13 @@
 // The whole chain runs on its own stream beside the sparse-coding kernel.
 // Wide cubes (256 < B <= 512, svt_wide.h): 1 and 5 are tiled over column panels, and 2-4 run on the
 // packed triangle in the workspace whatever solver the caller asked for, unless LRS_SVT_WIDE_TRI asks
-// for 3' over many workgroups with its certificate as GEMMs on the fp64 matrix cores (svt_wide_eig.h).
+// for 3' over many workgroups with its certificate as GEMMs on the fp64 matrix cores (svt_wide_eig.h);
+// LRS_SVT_WIDE_MW beside it spreads that chain's Householder reduction over many workgroups too, one
+// launch per column (svt_wide_mw.h).
 //
 // The stages: svt_gram.h (1, 2), svt_jacobi.h (3, 4), svt_eig.h (3'), svt_apply.h (5), svt_wide.h (the
-// wide Gram), svt_wide_eig.h (the wide 3'); svt_ws.h has the workspace and the table of which form
-// serves which band count.  Here: the launchers and the C entry points.
+// wide Gram), svt_wide_eig.h (the wide 3'), svt_wide_mw.h (its many-workgroup reduction); svt_ws.h has
+// the workspace and the table of which form serves which band count.  Here: the launchers and the C entry points.
 #include <algorithm>
 
 #include "lrs_common.h"
@@ -31,6 +33,7 @@
 #include "svt_jacobi.h"
 #include "svt_wide.h"
 #include "svt_wide_eig.h"
+#include "svt_wide_mw.h"
 #include "svt_ws.h"
 
 using namespace lrs;
@@ -81,11 +84,15 @@ static int svt_shape_check(int64_t B, int warm) {
     return LRS_OK;
 }
 
-// The flag word as the launchers read it: LRS_SVT_WIDE_TRI means something above kMaxBp only.
-static int svt_flags(int64_t B, int warm) { return svt_shape(B).wide ? warm : warm & ~LRS_SVT_WIDE_TRI; }
 // The wide tridiagonal chain (svt_wide_eig.h) serves; an explicit LRS_SVT_JACOBI wins.
 static bool svt_wide_tri(int64_t B, int warm) {
     return svt_shape(B).wide && (warm & LRS_SVT_WIDE_TRI) && !(warm & LRS_SVT_JACOBI);
+}
+// The flag word as the launchers read it: LRS_SVT_WIDE_TRI means something above kMaxBp only, and
+// LRS_SVT_WIDE_MW only where the wide tridiagonal chain serves.
+static int svt_flags(int64_t B, int warm) {
+    if (!svt_shape(B).wide) warm &= ~LRS_SVT_WIDE_TRI;
+    return svt_wide_tri(B, warm) ? warm : warm & ~LRS_SVT_WIDE_MW;
 }
 
 extern "C" int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, int64_t *ld) {
@@ -107,7 +114,7 @@ extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64
     const bool wide_tri = svt_wide_tri(B, warm);
     warm = svt_flags(B, warm);
     if (!warm || (wide_tri && !(warm & LRS_SVT_WARM))) {
-        hipError_t e = hipMemsetAsync(w.state, 0, sizeof(int) * 4, st);
+        hipError_t e = hipMemsetAsync(w.state, 0, sizeof(int) * 8, st);   // words 0-3, and 4-7 (every solve rewrites 4-6)
         if (e != hipSuccess) return (int)e;
     }
     const int Bp = (int)w.Bp;
@@ -174,8 +181,16 @@ extern "C" int lrs_svt_finish_f32(const float *X, const float *L2, float c2, int
         hipError_t ea = opt_in((const void *)k_svt_eig_wide_fb_vrebuild, vsmem);
         if (ea != hipSuccess) return (int)ea;
         const dim3 g64((unsigned)((Bp + 63) / 64), (unsigned)((Bp + 63) / 64));
-        hipLaunchKernelGGL(k_svt_eig_wide_tri, dim3(1), dim3(kEigThreads), sizeof(double) * Bp, st, w);
-        LRS_CHECK_LAUNCH();
+        if (warm & LRS_SVT_WIDE_MW) {
+            // the reduction over many workgroups: launch k forms reflector k + 1 and applies reflector k
+            for (int kc = -1; kc <= Bp - 2; ++kc) {
+                hipLaunchKernelGGL(k_svt_eig_wide_mw, dim3((unsigned)mw_nwg(Bp, kc)), dim3(kMwThreads), 0, st, w, kc);
+                LRS_CHECK_LAUNCH();
+            }
+        } else {
+            hipLaunchKernelGGL(k_svt_eig_wide_tri, dim3(1), dim3(kEigThreads), sizeof(double) * Bp, st, w);
+            LRS_CHECK_LAUNCH();
+        }
         hipLaunchKernelGGL(k_svt_eig_wide_vals, dim3((unsigned)((4 * Bp + kEigMwThreads - 1) / kEigMwThreads)),
                            dim3(kEigMwThreads), 0, st, w);
         LRS_CHECK_LAUNCH();
@@ -264,8 +279,8 @@ extern "C" int lrs_svt_f32(const float *X, const float *L2, float c2, int64_t P,
 
 // Diagnostics (not in include/lrspnp.h): state words of the last call (host copy): V valid, V buffer,
 // Jacobi rounds, sweeps, path (1 tridiagonal, 2 Jacobi fallback, 3 Jacobi, 4 wide tridiagonal, 5 its
-// Jacobi fallback), Newton-Schulz steps and certificate flag of the wide tridiagonal chain; words 7-31
-// are spare.
+// Jacobi fallback), Newton-Schulz steps and certificate flag of the wide tridiagonal chain, and word 7:
+// 1 when LRS_SVT_WIDE_MW's reduction produced that chain's triangle; words 8-31 are spare.
 extern "C" int lrs_diag_svt_state(void *ws, int64_t P, int64_t B, int *out32) {
     if (!ws || !out32 || P <= 0 || B <= 0) return LRS_E_INVALID;
     if (svt_shape_check(B, 0) != LRS_OK) return LRS_E_UNSUPPORTED;

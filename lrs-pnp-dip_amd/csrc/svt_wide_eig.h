@@ -4,7 +4,9 @@
 // GEMMs on the fp64 matrix cores over many workgroups.  One launch per phase, no host
 // synchronisation in between:
 // (kernel names below without their k_svt_eig_wide prefix)
-//   _tri                       A. G -> packed triangle in w.A0, reduced in place (one workgroup)
+//   _tri                       A. G -> packed triangle in w.A0, reduced in place (one workgroup);
+//                              with LRS_SVT_WIDE_MW instead n launches of _mw (svt_wide_mw.h): the same
+//                              reduction with the trailing matrix's rows over many workgroups
 //   _vals, _vecs               B, C. as k_svt_eig_vals / _vecs; residuals and ||T|| -> w.partial
 //   _back                      E. V[0] = H_0 ... H_{n-3} W
 //   _gemm<false>, _cert        D. S = V^T V -> w.A0 (the packed triangle is dead), then the
@@ -29,6 +31,7 @@ namespace lrs {
 // state words of the chain (svt_ws.h lists all of them)
 constexpr int kWtNs = 5;     // Newton-Schulz steps the last solve ran
 constexpr int kWtFlag = 6;   // certificate: kWtDone, kWtStep (one more Newton-Schulz step), kWtBad (fallback)
+constexpr int kWtMw = 7;     // 1: the many-workgroup reduction (svt_wide_mw.h) produced the triangle, 0: _tri
 constexpr int kWtDone = 0, kWtStep = 1, kWtBad = 2;
 constexpr int kWtMaxNs = 3;
 constexpr int kWtNv = 8;     // registers of a wave-distributed vector: 64 * 8 = kWideMaxBp columns
@@ -37,6 +40,7 @@ __global__ __launch_bounds__(kEigThreads) void k_svt_eig_wide_tri(SvtWs w) {
     extern __shared__ double sm[];   // [n] p vector
     __shared__ double shb[2];
     const int n = (int)w.Bp;
+    if (threadIdx.x == 0) w.state[kWtMw] = 0;
     eig_load_packed(w.G, w.A0, n);
     __syncthreads();
     eig_tridiag<true, kWtNv>(w.A0, sm, shb, n, w.beta);

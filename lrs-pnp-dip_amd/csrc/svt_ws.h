@@ -69,7 +69,8 @@ struct SvtWs {
     int *state;       // [0] V valid, [1] current V buffer, [2] rounds, [3] sweeps,
                       // [4] path of the last solve (1 tridiagonal, 2 Jacobi fallback, 3 Jacobi, 4 wide
                       // tridiagonal, 5 its Jacobi fallback), [5] Newton-Schulz steps and [6] certificate
-                      // flag of the wide tridiagonal chain (svt_wide_eig.h)
+                      // flag of the wide tridiagonal chain (svt_wide_eig.h), [7] 1 when that chain's triangle
+                      // came from the many-workgroup reduction (svt_wide_mw.h)
     int64_t Bp;
 };
 
@@ -79,6 +80,14 @@ struct SvtWs {
 // Bp = 258, 8.4 MB at 512) is the head of rot (kMaxSweeps (Bp - 1) (Bp / 2) 16 B: 21 MB and 84 MB).
 // F is written and read by the inverse iteration alone and is dead before the chain's Jacobi
 // fallback, the only writer of the rotation log in that call, starts.
+// The many-workgroup Householder reduction (LRS_SVT_WIDE_MW, svt_wide_mw.h) has no region either.  It
+// runs between k_gram_reduce16 and k_svt_eig_wide_vals and takes
+//   * the head of partial, 2 x kMwWgs x Bp doubles (256 KB at Bp = 512 of >= 10 MB), for the
+//     workgroups' partial vectors of A_sub v, double-buffered by column parity: the Gram partials are
+//     dead once k_gram_reduce16 has written G, and partial[0 .. Bp] (residuals, ||T||) is next
+//     written by k_svt_eig_wide_vecs, after the reduction's last launch;
+//   * the head of T, 2 x (Bp + 8) doubles, for the reflector in flight (v, beta, e, d), also by
+//     column parity: T is unused until k_svt_eig_wide_vecs writes W into it.
 struct SvtWsOffsets {
     size_t state, partial, G, A0, T, V[2], lam, rot, beta, F, Fp, E, total;
 };

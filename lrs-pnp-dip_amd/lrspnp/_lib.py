@@ -32,7 +32,7 @@ DIP_F32, DIP_SPLIT_BF16 = 0, 1
 ISTA_ALGO_AUTO, ISTA_ALGO_GENERIC = 0, 1
 
 # flag word (`warm`) of the SVT calls
-SVT_WARM, SVT_JACOBI, SVT_MULTI_WG, SVT_WIDE_TRI = 1, 2, 4, 8
+SVT_WARM, SVT_JACOBI, SVT_MULTI_WG, SVT_WIDE_TRI, SVT_WIDE_MW = 1, 2, 4, 8, 16
 
 
 class IstaOpts(ctypes.Structure):

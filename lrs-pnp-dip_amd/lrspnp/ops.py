@@ -12,7 +12,7 @@ import torch
 
 from . import _lib as _libmod
 from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLAB, PROX_SOFT, SVT_JACOBI, SVT_MULTI_WG,
-                   SVT_WARM, SVT_WIDE_TRI, LrsError, check, device_lib, lib)
+                   SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, LrsError, check, device_lib, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
            "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "masked_mse", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
@@ -321,22 +321,24 @@ def svt_workspace(P: int, B: int, device) -> torch.Tensor:
     return torch.zeros(n, dtype=torch.uint8, device=device)
 
 
-def _svt_flags(warm, method, multi_wg=False, wide_tri=False):
+def _svt_flags(warm, method, multi_wg=False, wide_tri=False, wide_mw=False):
     if method not in ("tri", "jacobi"):
         raise LrsError(f"unknown SVT eigensolver {method!r} (tri | jacobi)")
     return ((SVT_WARM if warm else 0) | (SVT_JACOBI if method == "jacobi" else 0) | (SVT_MULTI_WG if multi_wg else 0)
-            | (SVT_WIDE_TRI if wide_tri else 0))
+            | (SVT_WIDE_TRI if wide_tri else 0) | (SVT_WIDE_MW if wide_mw else 0))
 
 
 def svt(X, L2, c2: float, tau: float, ws, U=None, s_out=None, warm=False, stream=None, method="tri",
-        multi_wg=False, wide_tri=False):
+        multi_wg=False, wide_tri=False, wide_mw=False):
     """U = SVT(X + c2*L2, tau) (main_LRS_PnP.py:118-124).  method 'tri': tridiagonal eigensolver
     with a certified Jacobi fallback (default); 'jacobi': Jacobi only (warm-startable).  multi_wg:
     the tridiagonal solver's eigenvalue / eigenvector / back-transformation phases over many
     workgroups (LRS_SVT_MULTI_WG, bit-identical).  Wide cubes (256 < B <= svt_max_bands()) take
     the Jacobi solver, warm-started when `warm` is set, unless wide_tri (LRS_SVT_WIDE_TRI) asks for
     their tridiagonal chain (state path 4, or 5 after its Jacobi fallback; method 'jacobi' wins;
-    ignored at B <= 256); multi_wg is refused there."""
+    ignored at B <= 256); multi_wg is refused there.  wide_mw (LRS_SVT_WIDE_MW) beside wide_tri: that
+    chain with its Householder reduction over many workgroups, one launch per column (state word 7 is
+    then 1); ignored wherever the wide tridiagonal chain does not serve."""
     L = device_lib()
     _dev(X, torch.float32, "X")
     if L2 is not None:
@@ -345,17 +347,17 @@ def svt(X, L2, c2: float, tau: float, ws, U=None, s_out=None, warm=False, stream
     if U is None:
         U = torch.empty_like(X)
     check(L.lrs_svt_f32(_p(X), _p(L2), float(c2), P, B, float(tau), _p(U), _p(s_out),
-                        _svt_flags(warm, method, multi_wg, wide_tri), _p(ws), ws.numel(), _s(stream)), "lrs_svt_f32")
+                        _svt_flags(warm, method, multi_wg, wide_tri, wide_mw), _p(ws), ws.numel(), _s(stream)), "lrs_svt_f32")
     return U
 
 
-def svt_gram(X, L2, c2: float, ws, warm=False, stream=None, method="tri", wide_tri=False):
-    """First half of svt(): fp64 Gram (+ the Jacobi warm-start product, which wide_tri does without),
-    multi-workgroup."""
+def svt_gram(X, L2, c2: float, ws, warm=False, stream=None, method="tri", wide_tri=False, wide_mw=False):
+    """First half of svt(): fp64 Gram (+ the Jacobi warm-start product, which wide_tri does without,
+    with or without wide_mw), multi-workgroup."""
     L = device_lib()
     P, B = X.shape
-    check(L.lrs_svt_gram_f32(_p(X), _p(L2), float(c2), P, B, _svt_flags(warm, method, wide_tri=wide_tri), _p(ws),
-                             ws.numel(), _s(stream)), "lrs_svt_gram_f32")
+    check(L.lrs_svt_gram_f32(_p(X), _p(L2), float(c2), P, B, _svt_flags(warm, method, wide_tri=wide_tri, wide_mw=wide_mw),
+                             _p(ws), ws.numel(), _s(stream)), "lrs_svt_gram_f32")
 
 
 def svt_gram_view(ws, P: int, B: int) -> torch.Tensor:
@@ -368,13 +370,14 @@ def svt_gram_view(ws, P: int, B: int) -> torch.Tensor:
 
 
 def svt_finish(X, L2, c2: float, tau: float, ws, U, s_out=None, warm=False, stream=None, method="tri",
-               multi_wg=False, wide_tri=False):
+               multi_wg=False, wide_tri=False, wide_mw=False):
     """Second half of svt(): the eigensolver (one workgroup, or multi_wg; wide cubes: the Jacobi chain,
-    or with wide_tri their tridiagonal chain), E, then U = Z - Z E."""
+    or with wide_tri their tridiagonal chain, whose reduction wide_mw spreads over many workgroups), E,
+    then U = Z - Z E."""
     L = device_lib()
     P, B = X.shape
     check(L.lrs_svt_finish_f32(_p(X), _p(L2), float(c2), P, B, float(tau), _p(U), _p(s_out),
-                               _svt_flags(warm, method, multi_wg, wide_tri), _p(ws), ws.numel(), _s(stream)),
+                               _svt_flags(warm, method, multi_wg, wide_tri, wide_mw), _p(ws), ws.numel(), _s(stream)),
           "lrs_svt_finish_f32")
     return U
 
@@ -382,8 +385,9 @@ def svt_finish(X, L2, c2: float, tau: float, ws, U, s_out=None, warm=False, stre
 def svt_state(ws, P: int, B: int):
     """The 32 state words of the last SVT call: V valid, V buffer, Jacobi rounds, sweeps, path (1 =
     tridiagonal, 2 = Jacobi fallback, 3 = Jacobi, 4 = wide tridiagonal, 5 = its Jacobi fallback), and of
-    the wide tridiagonal chain its Newton-Schulz steps and certificate flag; words 7-31 are spare
-    (diagnostics; syncs)."""
+    the wide tridiagonal chain its Newton-Schulz steps, certificate flag and word 7: 1 when the
+    many-workgroup reduction (wide_mw) produced its triangle, 0 after the one-workgroup reduction; words
+    8-31 are spare (diagnostics; syncs)."""
     out = (ctypes.c_int * 32)()
     check(device_lib().lrs_diag_svt_state(_p(ws), P, B, ctypes.cast(out, ctypes.c_void_p)), "lrs_diag_svt_state")
     return list(out)

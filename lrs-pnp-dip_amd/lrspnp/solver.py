@@ -41,7 +41,8 @@ class LrsPnPConfig:
     # coding (a multi-launch chain there waits for free CUs between its launches).
     svt_multi_wg: str = "auto"
     # eigen stage of wide cubes (256 < B <= 512; ignored below): 'jacobi', the warm-started
-    # one-workgroup Jacobi chain, or 'tri', the tridiagonal chain over many workgroups (LRS_SVT_WIDE_TRI)
+    # one-workgroup Jacobi chain, 'tri', the tridiagonal chain over many workgroups (LRS_SVT_WIDE_TRI), or
+    # 'tri-mw', that chain with its Householder reduction over many workgroups too (+ LRS_SVT_WIDE_MW)
     svt_wide_solver: str = "jacobi"
     lowrank: str = "svt"          # 'svt' (main_LRS_PnP.py:315) or 'dip' (…1-LiP.py:399-411)
     dip: object = None            # lrspnp.dip.DipConfig for lowrank='dip' (None: reference defaults)
@@ -103,6 +104,15 @@ class LrsPnPConfig:
 
 _ALPHA = {"spec2": ops.ALPHA_SPEC2, "fro4": ops.ALPHA_FRO4, "soft": ops.ALPHA_SOFT, "matlab": ops.ALPHA_SPEC2}
 _PROX = {"spec2": ops.PROX_NLM, "fro4": ops.PROX_NLM, "soft": ops.PROX_SOFT, "matlab": ops.PROX_NLM_MATLAB}
+# LrsPnPConfig.svt_wide_solver -> (wide_tri, wide_mw) of the SVT calls
+_SVT_WIDE_SOLVER = {"jacobi": (False, False), "tri": (True, False), "tri-mw": (True, True)}
+
+
+def svt_wide_solver_flags(name):
+    """(wide_tri, wide_mw) for a value of LrsPnPConfig.svt_wide_solver (host-only)."""
+    if name not in _SVT_WIDE_SOLVER:
+        raise LrsError(f"unknown svt_wide_solver {name!r} ({' | '.join(_SVT_WIDE_SOLVER)})")
+    return _SVT_WIDE_SOLVER[name]
 
 
 class LrsPnP:
@@ -196,9 +206,8 @@ class LrsPnP:
             raise LrsError(f"unknown ista_dip_order {cfg.ista_dip_order!r} (beside | before)")
         if cfg.svt_multi_wg not in ("auto", "on", "off"):
             raise LrsError(f"unknown svt_multi_wg {cfg.svt_multi_wg!r} (auto | on | off)")
-        if cfg.svt_wide_solver not in ("jacobi", "tri"):
-            raise LrsError(f"unknown svt_wide_solver {cfg.svt_wide_solver!r} (jacobi | tri)")
-        self.svt_wide_tri = self.svt_wide and cfg.svt_wide_solver == "tri"
+        wide_tri, wide_mw = svt_wide_solver_flags(cfg.svt_wide_solver)
+        self.svt_wide_tri, self.svt_wide_mw = self.svt_wide and wide_tri, self.svt_wide and wide_mw
         if self.K <= 512 and (cfg.ista_patterns == "on" or (
                 cfg.ista_patterns == "auto" and ops.ista_pat_preferred(n, self.K, self.nb, self.npat, cfg.Nit))):
             plan, self.pat_ntiles = ops.ista_pat_plan(inv.reshape(-1), self.npat)
@@ -296,7 +305,8 @@ class LrsPnP:
     def low_rank(self, stream=None, s_out=None):
         warm = self.cfg.svt_warm and self.iteration > 0
         return ops.svt(self.X, self.L2, self.c2, self.tau, self.svt_ws, U=self.U, s_out=s_out, warm=warm,
-                       stream=stream, method=self.cfg.svt_method, wide_tri=self.svt_wide_tri)
+                       stream=stream, method=self.cfg.svt_method, wide_tri=self.svt_wide_tri,
+                       wide_mw=self.svt_wide_mw)
 
     def low_rank_dip(self, stream):
         """U = DIP(X + L2/mu2) (…1-LiP.py:399-411) on `stream`; the host polls early stopping."""
@@ -320,7 +330,7 @@ class LrsPnP:
         stream_wait(lr, main)
         # low-rank prox, first half (whole chip, ~0.2 ms): fp64 Gram (+ Jacobi warm-start products)
         ops.svt_gram(self.X, self.L2, self.c2, self.svt_ws, warm=warm, stream=lr, method=self.cfg.svt_method,
-                     wide_tri=self.svt_wide_tri)
+                     wide_tri=self.svt_wide_tri, wide_mw=self.svt_wide_mw)
         if self.comm is not None:
             self.comm.allreduce_(self.gram, lr)       # the cube's Gram = sum of the slabs' Grams
         gram_done = lr.record_event()
@@ -330,7 +340,7 @@ class LrsPnP:
             raise LrsError(f"unknown svt_multi_wg {mw!r} (auto | on | off)")
         ops.svt_finish(self.X, self.L2, self.c2, self.tau, self.svt_ws, self.U, warm=warm, stream=lr,
                        method=self.cfg.svt_method, multi_wg=mw == "on" or (mw == "auto" and self.comm is not None),
-                       wide_tri=self.svt_wide_tri)
+                       wide_tri=self.svt_wide_tri, wide_mw=self.svt_wide_mw)
         ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
                    stream=main)
         if self.cfg.svt_gram_first or self.cfg.svt_method == "jacobi" or self.svt_wide:

@@ -12,9 +12,11 @@ Per shape, median of --reps:
   apply       the apply kernel alone (lrs_diag_svt_apply)
   sweeps      Jacobi sweeps cold / warm (0 on the tridiagonal path)
 At B = 256 both solvers of the existing path are timed: 'tri' (the default there; no warm start) and
-'jacobi' (the chain the wide cubes run).  Every wide shape is timed with both of its eigen stages: the
-default Jacobi chain ('tri' row, path 3) and the tridiagonal chain of LRS_SVT_WIDE_TRI ('wide_tri' row,
-path 4; its "warm" column is the same cold chain on the perturbed matrix: it takes no warm start).
+'jacobi' (the chain the wide cubes run).  Every wide shape is timed with its three eigen stages: the
+default Jacobi chain ('tri' row, path 3), the tridiagonal chain of LRS_SVT_WIDE_TRI ('wide_tri' row,
+path 4; its "warm" column is the same cold chain on the perturbed matrix: it takes no warm start) and
+that chain with the many-workgroup Householder reduction of LRS_SVT_WIDE_MW ('wide_mw' row, path 4,
+state word 7 set).
 """
 import argparse
 import json
@@ -49,7 +51,7 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
-def shape(P, B, method, wide_tri=False):
+def shape(P, B, method, wide_tri=False, wide_mw=False):
     rng = np.random.default_rng(P + B)
     Z = rng.random((P, 8)) @ rng.random((8, B)) * 0.3 + 0.02 * rng.standard_normal((P, B))
     X = torch.from_numpy(Z.astype(np.float32)).cuda()
@@ -57,7 +59,7 @@ def shape(P, B, method, wide_tri=False):
     L2 = torch.from_numpy((0.01 * rng.standard_normal((P, B))).astype(np.float32)).cuda()
     U = torch.empty_like(X)
     ws = ops.svt_workspace(P, B, "cuda")
-    kw = {"method": method, "wide_tri": wide_tri}
+    kw = {"method": method, "wide_tri": wide_tri, "wide_mw": wide_mw}
     ops.svt(X, L2, C2, TAU, ws, U=U, **kw)   # first launches (module load, LDS opt-in)
     torch.cuda.synchronize()
     t = {k: [] for k in ("gram", "gram_warm", "fin_cold", "fin_warm", "apply")}
@@ -75,7 +77,9 @@ def shape(P, B, method, wide_tri=False):
             sweeps[1] = state[3] if state[4] != 4 else 0
         t["apply"].append(timed(lambda: ops.svt_apply_only(X2, L2, C2, ws, U)))
     m = {k: float(np.median(v)) if v else None for k, v in t.items()}
-    return {"P": P, "B": B, "method": "wide_tri" if wide_tri else method, "path": path, "ws_MB": ws.numel() / 1e6,
+    assert state[7] == int(wide_mw), state[:8]
+    return {"P": P, "B": B, "method": "wide_mw" if wide_mw else "wide_tri" if wide_tri else method, "path": path,
+            "ws_MB": ws.numel() / 1e6,
             "gram_ms": m["gram"], "gram_warm_ms": m["gram_warm"],
             "eig_cold_ms": m["fin_cold"] - m["apply"],
             "eig_warm_ms": m["fin_warm"] - m["apply"] if warmable else None,
@@ -86,6 +90,7 @@ rows = [shape(a.P, 256, "tri"), shape(a.P, 256, "jacobi")]
 for B in (320, 448, 512):
     rows.append(shape(a.P, B, "tri"))
     rows.append(shape(a.P, B, "tri", wide_tri=True))
+    rows.append(shape(a.P, B, "tri", wide_tri=True, wide_mw=True))
 f = lambda v: "     -" if v is None else f"{v:6.0f}" if isinstance(v, int) else f"{v:9.3f}"
 print(f"{'P':>6} {'B':>4} {'solver':>8} {'path':>4} {'ws MB':>9} {'gram':>9} {'gram warm':>9} {'eig cold':>9} "
       f"{'eig warm':>9} {'apply':>9} {'sweeps c/w':>10}   (ms, median of {a.reps})")
