@@ -380,12 +380,28 @@ int lrs_masked_mse_f32(const float *out, const float *target, const float *mask,
  * (1,1,H,W); the mean stays over all C*P elements.  Any other count: LRS_E_INVALID. */
 int lrs_masked_mse_cmask_f32(const float *out, const float *target, const float *mask, int mask_channels,
                              int C, int64_t P, float *gout, double *loss_acc, void *stream);
+/* The same for an output that holds its image inside a frame (lrs_dipnet_set_frame): the mask is 0 on
+ * the frame, so the sum runs over the image alone and gout is 0 on the frame; gout = dL/dout of the mean
+ * over n_mean elements (the image's C*H*W, 0 < n_mean <= C*P) instead of C*P.  n_mean = C*P is
+ * lrs_masked_mse_cmask_f32, launch for launch. */
+int lrs_masked_mse_framed_f32(const float *out, const float *target, const float *mask, int mask_channels,
+                              int C, int64_t P, int64_t n_mean, float *gout, double *loss_acc, void *stream);
 
 /* Layout transforms between the unfolded matrix X[p = i + H j][b] and the DIP image img[b][i][j]
  * (…1-LiP.py:404 DIP_input = X + (1/mu_2) lambda_2 as (1,B,H,W); :411 U back to (P,B)). */
 int lrs_unfolded_to_image_f32(const float *X, const float *L, float c, int64_t H, int64_t W, int64_t B,
                               float *img, void *stream);
 int lrs_image_to_unfolded_f32(const float *img, int64_t H, int64_t W, int64_t B, float *X, void *stream);
+/* The same two for an image held inside a frame: img is [B][Hf][Wf] with the H x W image at rows
+ * top.., columns left...  _to_frame also fills the frame by reflection without repeating the edge
+ * (nn.ReflectionPad2d((left, Wf-W-left, top, Hf-H-top)) of the image), in the one pass that reads the
+ * unfolded rows; _frame_to_unfolded reads the interior only.  Every pad must be smaller than the
+ * dimension it mirrors (ReflectionPad2d's own rule): LRS_E_INVALID otherwise.  An extension: the
+ * reference has no frame (its net refuses the sizes that need one). */
+int lrs_unfolded_to_frame_f32(const float *X, const float *L, float c, int64_t H, int64_t W, int64_t B,
+                              int64_t top, int64_t left, int64_t Hf, int64_t Wf, float *img, void *stream);
+int lrs_frame_to_unfolded_f32(const float *img, int64_t H, int64_t W, int64_t B, int64_t top, int64_t left,
+                              int64_t Hf, int64_t Wf, float *X, void *stream);
 
 /* Early stopping state (device memory).  lrs_es_init fills it; every lrs_es_update_f32 pushes one
  * output into the ring and, once full, applies the variance test.  ring: lrs_es_ring_bytes(size, N)
@@ -448,6 +464,17 @@ int lrs_dipnet_forward(lrs_dipnet *net, const float *x, void *stream);
 int lrs_dipnet_backward(lrs_dipnet *net, const float *x, const float *gout, void *stream);
 /* ln_lambda of the spectral normalisation (my_Lipschitz_Unet(..., ln_lambda); default 1) */
 int lrs_dipnet_set_ln_lambda(lrs_dipnet *net, float ln_lambda);
+/* The image inside the net's output: H x W pixels at (top, left) of the Ho x Wo output, for a net
+ * trained on an image of a size it does not reproduce, padded to one it does.  The target's and the
+ * input's frame contents are the caller's (lrs_unfolded_to_frame_f32); the mask must be 0 on the frame.
+ * With a frame set, lrs_dipnet_train_steps* take the loss as the mean over the image's C*H*W elements
+ * (gradient and lrs_dipnet_last_loss alike), and es / ring see the image only: ring is sized for
+ * N = C*H*W and holds the cropped outputs [C][H][W].  Call it between steps (it is part of the captured
+ * graph's key).  The whole output (0, 0, Ho, Wo), the state after lrs_dipnet_create, is no frame: the
+ * step then launches exactly the kernels it launches without this call.  Every pad must be smaller
+ * than the dimension it mirrors. */
+int lrs_dipnet_set_frame(lrs_dipnet *net, int top, int left, int H, int W);
+int lrs_dipnet_get_frame(const lrs_dipnet *net, int *top, int *left, int *H, int *W);
 const float *lrs_dipnet_output(const lrs_dipnet *net);
 const float *lrs_dipnet_grads(const lrs_dipnet *net);
 /* diagnostics: node i's buffers in the workspace after a forward / backward (NULL where absent):

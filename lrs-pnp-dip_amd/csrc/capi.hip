@@ -5,7 +5,7 @@
 
 #include "lrs_common.h"
 
-extern "C" const char *lrs_version(void) { return "lrspnp-hip 0.2.0 (gfx950)"; }
+extern "C" const char *lrs_version(void) { return "lrspnp-hip 0.2.1 (gfx950)"; }
 
 extern "C" int lrs_check_device(void) {
     int dev = 0;

@@ -1603,11 +1603,11 @@ __global__ void k_sn_apply(const SnConv *convs, const float *scale) {
 // grid (S, C): workgroup (sb, c) covers pixels [sb*chunk, +chunk) of channel c, so the mask
 // index is c * mstride + the pixel (no 64-bit modulo); vec: float4 loads / stores (P, chunk
 // multiples of 4; with mstride = P the mask rows are 16-B aligned as those of out and target are).
-__global__ __launch_bounds__(256) void k_masked_mse(const float *__restrict__ out, const float *__restrict__ target,
-                                                    const float *__restrict__ mask, int64_t mstride, int C, int64_t P,
-                                                    int chunk, int vec, float *__restrict__ gout, double *loss_acc) {
+// (the body of both kernels below; norm = 2 / the element count of the mean)
+__device__ __forceinline__ void masked_mse_body(const float *__restrict__ out, const float *__restrict__ target,
+                                                const float *__restrict__ mask, int64_t mstride, int64_t P, int chunk,
+                                                int vec, float *__restrict__ gout, double *loss_acc, const float norm) {
     __shared__ double red[8];
-    const float norm = (float)(2.0 / ((double)C * (double)P));
     const int64_t off = (int64_t)blockIdx.y * P;
     const float *mrow = mask ? mask + (int64_t)blockIdx.y * mstride : nullptr;   // this channel's mask row
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(P, i0 + chunk);
@@ -1643,6 +1643,21 @@ __global__ __launch_bounds__(256) void k_masked_mse(const float *__restrict__ ou
     if (threadIdx.x == 0) atomicAdd(loss_acc, s);
 }
 
+__global__ __launch_bounds__(256) void k_masked_mse(const float *__restrict__ out, const float *__restrict__ target,
+                                                    const float *__restrict__ mask, int64_t mstride, int C, int64_t P,
+                                                    int chunk, int vec, float *__restrict__ gout, double *loss_acc) {
+    masked_mse_body(out, target, mask, mstride, P, chunk, vec, gout, loss_acc, (float)(2.0 / ((double)C * (double)P)));
+}
+
+// The same over a framed output: the mask is 0 on the frame, so those elements add nothing to the sum
+// and get gout = 0; the mean is over the n_mean interior elements (lrs_dipnet_set_frame) instead of C P.
+__global__ __launch_bounds__(256) void k_masked_mse_n(const float *__restrict__ out, const float *__restrict__ target,
+                                                      const float *__restrict__ mask, int64_t mstride, int64_t n_mean,
+                                                      int64_t P, int chunk, int vec, float *__restrict__ gout,
+                                                      double *loss_acc) {
+    masked_mse_body(out, target, mask, mstride, P, chunk, vec, gout, loss_acc, (float)(2.0 / (double)n_mean));
+}
+
 // Loss head of a training step whose last node is a conv without BN (both reference nets): the
 // masked MSE (as k_masked_mse: sum d^2, dL/dout = -(2/(C P)) d m) fused with that node's
 // activation backward dL/dz = act'(out) dL/dout and its bias gradient sum_p dL/dz: one pass
@@ -1652,15 +1667,13 @@ __global__ __launch_bounds__(256) void k_masked_mse(const float *__restrict__ ou
 // finish (per-channel counter) sums that channel's partials in order, the last channel to finish
 // (counter cnt[C]) sums the channel losses in order into loss_acc: bias gradient and loss are both
 // deterministic.  Counters are reset by their last arriver.
-__global__ __launch_bounds__(256) void k_mse_head(const float *__restrict__ out, const float *__restrict__ target,
-                                                  const float *__restrict__ mask, int64_t mstride, int C,
-                                                  int64_t P, int chunk, int vec, int act,
-                                                  float *__restrict__ gz, double *loss_acc,
-                                                  double *__restrict__ part, int *__restrict__ cnt,
-                                                  float *__restrict__ gbias) {
+__device__ __forceinline__ void mse_head_body(const float *__restrict__ out, const float *__restrict__ target,
+                                              const float *__restrict__ mask, int64_t mstride, int C, int64_t P,
+                                              int chunk, int vec, int act, float *__restrict__ gz, double *loss_acc,
+                                              double *__restrict__ part, int *__restrict__ cnt,
+                                              float *__restrict__ gbias, const float norm) {
     __shared__ double red[8];
     __shared__ int last;
-    const float norm = (float)(2.0 / ((double)C * (double)P));
     const int c = blockIdx.y, S = gridDim.x;
     const int64_t off = (int64_t)c * P;
     const float *mrow = mask ? mask + (int64_t)c * mstride : nullptr;   // as k_masked_mse: [P] or [C][P]
@@ -1743,6 +1756,27 @@ __global__ __launch_bounds__(256) void k_mse_head(const float *__restrict__ out,
         *loss_acc += tot;
         agent_store(cnt + C, 0);
     }
+}
+
+__global__ __launch_bounds__(256) void k_mse_head(const float *__restrict__ out, const float *__restrict__ target,
+                                                  const float *__restrict__ mask, int64_t mstride, int C,
+                                                  int64_t P, int chunk, int vec, int act,
+                                                  float *__restrict__ gz, double *loss_acc,
+                                                  double *__restrict__ part, int *__restrict__ cnt,
+                                                  float *__restrict__ gbias) {
+    mse_head_body(out, target, mask, mstride, C, P, chunk, vec, act, gz, loss_acc, part, cnt, gbias,
+                  (float)(2.0 / ((double)C * (double)P)));
+}
+
+// the head of a framed output (k_masked_mse_n): the mean over the n_mean interior elements
+__global__ __launch_bounds__(256) void k_mse_head_n(const float *__restrict__ out, const float *__restrict__ target,
+                                                    const float *__restrict__ mask, int64_t mstride, int C,
+                                                    int64_t P, int chunk, int vec, int act,
+                                                    float *__restrict__ gz, double *loss_acc,
+                                                    double *__restrict__ part, int *__restrict__ cnt,
+                                                    float *__restrict__ gbias, int64_t n_mean) {
+    mse_head_body(out, target, mask, mstride, C, P, chunk, vec, act, gz, loss_acc, part, cnt, gbias,
+                  (float)(2.0 / (double)n_mean));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1875,8 +1909,15 @@ __host__ __device__ inline int64_t es_ab_offset_bytes(int size, int64_t N) {   /
     return ((int64_t)size * N * 4 + 15) / 16 * 16;
 }
 
-__global__ __launch_bounds__(256) void k_es_step(const float *__restrict__ out, int64_t N, float *__restrict__ ring,
-                                                lrs_es_state *st) {
+// The interior of a framed output [C][Hf][Wf] as the ring sees it: element i = (c H + y) W + x of the
+// [C][H][W] interior lies at (c Hf + top + y) Wf + left + x (lrs_dipnet_set_frame; N <= INT32_MAX).
+struct EsCrop {
+    int top, left, H, W, Hf, Wf;
+};
+
+template <bool kCrop>
+__device__ __forceinline__ void es_step_body(const float *__restrict__ out, int64_t N, float *__restrict__ ring,
+                                             lrs_es_state *st, const EsCrop cr) {
     __shared__ double red[16];
     const int S = st->size, c = st->count, slot = c % S;   // c: this output's epoch (k_es_decide increments count)
     double *A = reinterpret_cast<double *>(reinterpret_cast<char *>(ring) + es_ab_offset_bytes(S, N));
@@ -1885,7 +1926,14 @@ __global__ __launch_bounds__(256) void k_es_step(const float *__restrict__ out, 
     const bool full = c + 1 >= S, refresh = es_refresh(c, S);
     double dq = 0.0, qa = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = out[i];
+        float x;
+        if (kCrop) {
+            const unsigned hw = (unsigned)(cr.H * cr.W), ch = (unsigned)i / hw, r = (unsigned)i - ch * hw;
+            const unsigned y = r / (unsigned)cr.W, xx = r - y * (unsigned)cr.W;
+            x = out[((int64_t)ch * cr.Hf + cr.top + y) * cr.Wf + cr.left + xx];
+        } else {
+            x = out[i];
+        }
         double a;
         if (refresh) {   // the ring in slot order, the new output in the last slot
             dst[i] = x;
@@ -1917,6 +1965,18 @@ __global__ __launch_bounds__(256) void k_es_step(const float *__restrict__ out, 
         part[blockIdx.x] = dq;
         part[kEsMaxBlocks + blockIdx.x] = qa;
     }
+}
+
+__global__ __launch_bounds__(256) void k_es_step(const float *__restrict__ out, int64_t N, float *__restrict__ ring,
+                                                lrs_es_state *st) {
+    es_step_body<false>(out, N, ring, st, EsCrop{});
+}
+
+// the same update fed the interior of a framed output: the ring, the window sums and the variance test
+// are those of the cropped [C][H][W] image (same workgroups, same order: bit-identical to k_es_step on a crop)
+__global__ __launch_bounds__(256) void k_es_step_crop(const float *__restrict__ out, int64_t N, float *__restrict__ ring,
+                                                     lrs_es_state *st, EsCrop cr) {
+    es_step_body<true>(out, N, ring, st, cr);
 }
 
 // one wave: the nblk partials of k_es_step in a fixed order, then the reference's patience test

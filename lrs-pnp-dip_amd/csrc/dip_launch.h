@@ -802,9 +802,15 @@ __global__ void k_es_init(lrs_es_state *st, int size, int patience) {
     st->last_var = NAN;
 }
 
-int es_update(const float *out, int64_t N, float *ring, lrs_es_state *es, hipStream_t st) {
+// cr: the update reads the interior of a framed output (N = C cr->H cr->W elements of it)
+int es_update(const float *out, int64_t N, float *ring, lrs_es_state *es, hipStream_t st, const EsCrop *cr = nullptr) {
     const unsigned nblk = ew_blocks(N, kEsMaxBlocks);
-    hipLaunchKernelGGL(k_es_step, dim3(nblk), dim3(kEw), 0, st, out, N, ring, es);
+    if (cr) {
+        if (N > INT32_MAX) return LRS_E_UNSUPPORTED;   // k_es_step_crop's 32-bit index map
+        hipLaunchKernelGGL(k_es_step_crop, dim3(nblk), dim3(kEw), 0, st, out, N, ring, es, *cr);
+    } else {
+        hipLaunchKernelGGL(k_es_step, dim3(nblk), dim3(kEw), 0, st, out, N, ring, es);
+    }
     hipLaunchKernelGGL(k_es_decide, dim3(1), dim3(64), 0, st, (const float *)ring, N, (int)nblk, es);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
@@ -853,6 +859,76 @@ __global__ void k_image_to_unfolded(const float *__restrict__ img, int64_t H, in
         const int64_t b = o % B, p = o / B;
         const int64_t i = p % H, j = p / H;
         X[o] = img[(b * H + i) * W + j];
+    }
+}
+
+// ---- the same two transforms for an image inside a reflected frame (lrs_dipnet_set_frame) --------
+// The image's H x W pixels sit at (top, left) of a Hf x Wf frame.  For one image row i both kernels
+// transpose a 32 (columns j) x 32 (bands b) tile through LDS, so the unfolded rows X[(i + H j) B + b]
+// are read / written along b and the image rows along j.
+constexpr int kFrTile = 32;
+
+struct FrameGeom {
+    int H, W, B, top, left, Hf, Wf;
+};
+
+// The destinations of source index s along one axis of n pixels padded by lo before / hi after
+// (ReflectionPad2d: the edge is not repeated): itself at lo + s, its mirror image in the leading pad
+// (1 <= s <= lo) and in the trailing pad (n - 1 - hi <= s <= n - 2).  lo, hi < n.
+__device__ __forceinline__ int frame_dests(int s, int n, int lo, int hi, int d[3]) {
+    int nd = 0;
+    d[nd++] = lo + s;
+    if (s >= 1 && s <= lo) d[nd++] = lo - s;
+    if (s >= n - 1 - hi && s <= n - 2) d[nd++] = 2 * (n - 1) + lo - s;
+    return nd;
+}
+
+// img[b][top + i][left + j] = X[(i + H j) B + b] + c * L[...], and every frame pixel that reflects onto
+// (i, j) in the same pass: the whole [B][Hf][Wf] image is written once, the unfolded rows are read once.
+// grid (ceil(W / 32), ceil(B / 32), H), block (32, 8)
+__global__ __launch_bounds__(256) void k_unfolded_to_frame(const float *__restrict__ X, const float *__restrict__ L,
+                                                           float c, FrameGeom g, float *__restrict__ img) {
+    __shared__ float tile[kFrTile][kFrTile + 1];   // [j][b]
+    const int i = blockIdx.z, j0 = blockIdx.x * kFrTile, b0 = blockIdx.y * kFrTile;
+    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along b
+        const int j = j0 + r, b = b0 + threadIdx.x;
+        if (j < g.W && b < g.B) {
+            const int64_t src = ((int64_t)i + (int64_t)g.H * j) * g.B + b;
+            float v = X[src];
+            if (L) v = v + c * L[src];
+            tile[r][threadIdx.x] = v;
+        }
+    }
+    __syncthreads();
+    int ys[3];
+    const int ny = frame_dests(i, g.H, g.top, g.Hf - g.H - g.top, ys);
+    const int j = j0 + threadIdx.x;
+    if (j >= g.W) return;
+    int xs[3];
+    const int nx = frame_dests(j, g.W, g.left, g.Wf - g.W - g.left, xs);
+    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along j
+        const int b = b0 + r;
+        if (b >= g.B) break;
+        const float v = tile[threadIdx.x][r];
+        float *plane = img + (int64_t)b * g.Hf * g.Wf;
+        for (int a = 0; a < ny; ++a)
+            for (int e = 0; e < nx; ++e) plane[(int64_t)ys[a] * g.Wf + xs[e]] = v;
+    }
+}
+
+// X[(i + H j) B + b] = img[b][top + i][left + j]: the interior of the framed image, unfolded
+__global__ __launch_bounds__(256) void k_frame_to_unfolded(const float *__restrict__ img, FrameGeom g,
+                                                           float *__restrict__ X) {
+    __shared__ float tile[kFrTile][kFrTile + 1];   // [b][j]
+    const int i = blockIdx.z, j0 = blockIdx.x * kFrTile, b0 = blockIdx.y * kFrTile;
+    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along j
+        const int b = b0 + r, j = j0 + threadIdx.x;
+        if (b < g.B && j < g.W) tile[r][threadIdx.x] = img[((int64_t)b * g.Hf + g.top + i) * g.Wf + g.left + j];
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along b
+        const int j = j0 + r, b = b0 + threadIdx.x;
+        if (j < g.W && b < g.B) X[((int64_t)i + (int64_t)g.H * j) * g.B + b] = tile[threadIdx.x][r];
     }
 }
 

@@ -236,9 +236,10 @@ static int64_t mask_stride(const float *mask, int mask_channels, int C, int64_t 
 // and the stride is a multiple of 4 floats (0, or P with P % 4 == 0)
 static bool mask_al16(const float *mask, int64_t mstride) { return !mask || (al16(mask) && mstride % 4 == 0); }
 
-extern "C" int lrs_masked_mse_cmask_f32(const float *out, const float *target, const float *mask, int mask_channels,
-                                        int C, int64_t P, float *gout, double *loss_acc, void *stream) {
-    if (!out || !target || !loss_acc || C <= 0 || P <= 0) return LRS_E_INVALID;
+// n_mean: the element count of the mean (C P, or fewer for a framed output: k_masked_mse_n)
+static int masked_mse(const float *out, const float *target, const float *mask, int mask_channels, int C, int64_t P,
+                      int64_t n_mean, float *gout, double *loss_acc, void *stream) {
+    if (!out || !target || !loss_acc || C <= 0 || P <= 0 || n_mean <= 0 || n_mean > (int64_t)C * P) return LRS_E_INVALID;
     const int64_t mstride = mask_stride(mask, mask_channels, C, P);
     if (mstride < 0) return LRS_E_INVALID;
     const int vec = (P % 4 == 0 && al16(out) && al16(target) && mask_al16(mask, mstride) && (!gout || al16(gout))) ? 1 : 0;
@@ -247,10 +248,25 @@ extern "C" int lrs_masked_mse_cmask_f32(const float *out, const float *target, c
     int64_t chunk = (P + S - 1) / S;
     if (vec) chunk = (chunk + 3) & ~(int64_t)3;
     if (chunk > INT32_MAX || C > 65535) return LRS_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_masked_mse, dim3((unsigned)S, (unsigned)C), dim3(256), 0, (hipStream_t)stream, out, target,
-                       mask, mstride, C, P, (int)chunk, vec, gout, loss_acc);
+    if (n_mean == (int64_t)C * P)
+        hipLaunchKernelGGL(k_masked_mse, dim3((unsigned)S, (unsigned)C), dim3(256), 0, (hipStream_t)stream, out, target,
+                           mask, mstride, C, P, (int)chunk, vec, gout, loss_acc);
+    else
+        hipLaunchKernelGGL(k_masked_mse_n, dim3((unsigned)S, (unsigned)C), dim3(256), 0, (hipStream_t)stream, out, target,
+                           mask, mstride, n_mean, P, (int)chunk, vec, gout, loss_acc);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
+}
+
+extern "C" int lrs_masked_mse_cmask_f32(const float *out, const float *target, const float *mask, int mask_channels,
+                                        int C, int64_t P, float *gout, double *loss_acc, void *stream) {
+    return masked_mse(out, target, mask, mask_channels, C, P, (int64_t)C * P, gout, loss_acc, stream);
+}
+
+extern "C" int lrs_masked_mse_framed_f32(const float *out, const float *target, const float *mask, int mask_channels,
+                                         int C, int64_t P, int64_t n_mean, float *gout, double *loss_acc,
+                                         void *stream) {
+    return masked_mse(out, target, mask, mask_channels, C, P, n_mean, gout, loss_acc, stream);
 }
 
 extern "C" int lrs_masked_mse_f32(const float *out, const float *target, const float *mask, int C, int64_t P,
@@ -271,6 +287,37 @@ extern "C" int lrs_image_to_unfolded_f32(const float *img, int64_t H, int64_t W,
     if (!X || !img || H <= 0 || W <= 0 || B <= 0) return LRS_E_INVALID;
     hipLaunchKernelGGL(k_image_to_unfolded, dim3(ew_blocks(H * W * B, 8192)), dim3(kEw), 0, (hipStream_t)stream,
                        img, H, W, B, X);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
+// a frame ReflectionPad2d accepts: the image inside it, every pad smaller than the dimension it mirrors
+static bool frame_ok(int64_t H, int64_t W, int64_t top, int64_t left, int64_t Hf, int64_t Wf) {
+    return H > 0 && W > 0 && top >= 0 && left >= 0 && top + H <= Hf && left + W <= Wf && Hf <= INT32_MAX / 4 &&
+           Wf <= INT32_MAX / 4 && top < H && Hf - H - top < H && left < W && Wf - W - left < W;
+}
+
+static dim3 frame_grid(int64_t H, int64_t W, int64_t B) {
+    return dim3((unsigned)((W + kFrTile - 1) / kFrTile), (unsigned)((B + kFrTile - 1) / kFrTile), (unsigned)H);
+}
+
+extern "C" int lrs_unfolded_to_frame_f32(const float *X, const float *L, float c, int64_t H, int64_t W, int64_t B,
+                                         int64_t top, int64_t left, int64_t Hf, int64_t Wf, float *img, void *stream) {
+    if (!X || !img || B <= 0 || !frame_ok(H, W, top, left, Hf, Wf)) return LRS_E_INVALID;
+    if (H > 65535 || (B + kFrTile - 1) / kFrTile > 65535) return LRS_E_UNSUPPORTED;
+    const FrameGeom g{(int)H, (int)W, (int)B, (int)top, (int)left, (int)Hf, (int)Wf};
+    hipLaunchKernelGGL(k_unfolded_to_frame, frame_grid(H, W, B), dim3(kFrTile, 8), 0, (hipStream_t)stream, X, L, c, g,
+                       img);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
+extern "C" int lrs_frame_to_unfolded_f32(const float *img, int64_t H, int64_t W, int64_t B, int64_t top, int64_t left,
+                                         int64_t Hf, int64_t Wf, float *X, void *stream) {
+    if (!X || !img || B <= 0 || !frame_ok(H, W, top, left, Hf, Wf)) return LRS_E_INVALID;
+    if (H > 65535 || (B + kFrTile - 1) / kFrTile > 65535) return LRS_E_UNSUPPORTED;
+    const FrameGeom g{(int)H, (int)W, (int)B, (int)top, (int)left, (int)Hf, (int)Wf};
+    hipLaunchKernelGGL(k_frame_to_unfolded, frame_grid(H, W, B), dim3(kFrTile, 8), 0, (hipStream_t)stream, img, g, X);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
@@ -399,7 +446,8 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
 }
 
 // the early-stopping update of this step's output, run beside the backward (dipnet_step)
-struct EsJob { const float *out; int64_t N; float *ring; lrs_es_state *es; };
+// (cr: the interior of a framed output, lrs_dipnet_set_frame; NULL without a frame)
+struct EsJob { const float *out; int64_t N; float *ring; lrs_es_state *es; const EsCrop *cr; };
 
 // k_mse_head over the last node (conv without BN): gz and the bias gradient of that node, + loss
 int mse_head(lrs_dipnet *net, const float *out, const float *target, const float *mask, int64_t mstride,
@@ -415,9 +463,14 @@ int mse_head(lrs_dipnet *net, const float *out, const float *target, const float
     // partials: bias [C][S], loss [C][S], channel losses [C]  (bn_part_doubles = 3 C bn_split(P))
     if (chunk > INT32_MAX || P > INT32_MAX || 2 * (int64_t)N.C * S + N.C > bn_part_doubles(N.C, P))
         return LRS_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_mse_head, dim3((unsigned)S, (unsigned)N.C), dim3(256), 0, st, out, target, mask, mstride, N.C,
-                       P, (int)chunk, vec, N.d.act, gz, net->loss_acc(), net->bnpart(), net->headcnt(),
-                       net->grads + N.b_off);
+    if (!net->framed)
+        hipLaunchKernelGGL(k_mse_head, dim3((unsigned)S, (unsigned)N.C), dim3(256), 0, st, out, target, mask, mstride, N.C,
+                           P, (int)chunk, vec, N.d.act, gz, net->loss_acc(), net->bnpart(), net->headcnt(),
+                           net->grads + N.b_off);
+    else
+        hipLaunchKernelGGL(k_mse_head_n, dim3((unsigned)S, (unsigned)N.C), dim3(256), 0, st, out, target, mask, mstride,
+                           N.C, P, (int)chunk, vec, N.d.act, gz, net->loss_acc(), net->bnpart(), net->headcnt(),
+                           net->grads + N.b_off, net->n_mean());
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
@@ -468,7 +521,7 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
     // weight gradients (its ring slot and window sums follow the previous step's there), joined before Adam
     auto es_side = [&](hipStream_t hs) -> int {
         if (!esj) return LRS_OK;
-        const int r = es_update(esj->out, esj->N, esj->ring, esj->es, hs);
+        const int r = es_update(esj->out, esj->N, esj->ring, esj->es, hs, esj->cr);
         esj = nullptr;
         return r;
     };
@@ -667,7 +720,9 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
     // the loss head in the last conv's epilogue (k_pw): gz, and per-workgroup sums for the bias gradient
     // and the loss, reduced in the backward on the side stream (k_mse_head's arithmetic per element)
     const PwHead hd{target, mask, mstride, net->f(Lst.gz_off), net->hpart(),
-                    (float)(2.0 / ((double)Lst.C * (double)Lst.P)), &net->head_nwg};
+                    net->framed ? (float)(2.0 / (double)net->n_mean())
+                                : (float)(2.0 / ((double)Lst.C * (double)Lst.P)),
+                    &net->head_nwg};
     // (k_pw's epilogue takes its float4 form when P % 4 == 0 and reads the mask rows as float4 there;
     // a [C][P] mask with P % 4 != 0 has unaligned rows and takes k_mse_head's scalar path instead)
     const bool fused_head = net->head_pw && mask_al16(mask, mstride) && al16(target);
@@ -680,14 +735,17 @@ int dipnet_step(lrs_dipnet *net, const float *x, const float *target, const floa
     } else if (net->head_fusable) {
         rc = mse_head(net, out, target, mask, mstride, st);
     } else {
-        rc = lrs_masked_mse_cmask_f32(out, target, mask, mstride ? Lst.C : 1, Lst.C, Lst.P, net->f(Lst.grad_off),
-                                      net->loss_acc(), st);
+        rc = masked_mse(out, target, mask, mstride ? Lst.C : 1, Lst.C, Lst.P, net->n_mean(), net->f(Lst.grad_off),
+                        net->loss_acc(), st);
     }
     if (rc) return rc;
     // the input conv's weight-gradient split-K sum is finished inside Adam (one launch less on the
     // step's tail)
     AdamPend pw{};
-    const EsJob esj{out, (int64_t)Lst.C * Lst.P, ring, es};
+    // (the early-stopping ring holds the interior of a framed output only: what the frame holds is
+    // constrained by nothing and must not drive the stop)
+    const EsCrop crop{net->fr_top, net->fr_left, net->fr_H, net->fr_W, Lst.H, Lst.W};
+    const EsJob esj{out, net->n_mean(), ring, es, net->framed ? &crop : nullptr};
     rc = dipnet_backward(net, x, st, net->head_fusable, &pw, fused_head, es ? &esj : nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL(k_adam, dim3(ew_blocks((net->n_params + 3) / 4, 8192)), dim3(kEw), 0, st, net->params,
@@ -752,6 +810,8 @@ extern "C" int lrs_dipnet_create(const lrs_dip_node *nodes, int n_nodes, int C, 
         delete net;
         return rc;
     }
+    net->fr_H = net->nodes.back().H;   // no frame: the whole output
+    net->fr_W = net->nodes.back().W;
     *out = net;
     return LRS_OK;
 }
@@ -906,6 +966,22 @@ extern "C" int lrs_dipnet_set_ln_lambda(lrs_dipnet *net, float ln_lambda) {
     return LRS_OK;
 }
 
+extern "C" int lrs_dipnet_set_frame(lrs_dipnet *net, int top, int left, int H, int W) {
+    if (!net) return LRS_E_INVALID;
+    const auto &Lst = net->nodes.back();
+    if (!frame_ok(H, W, top, left, Lst.H, Lst.W)) return LRS_E_INVALID;
+    net->fr_top = top; net->fr_left = left; net->fr_H = H; net->fr_W = W;
+    net->framed = H != Lst.H || W != Lst.W;   // the whole output: the unframed step, kernel for kernel
+    return LRS_OK;
+}
+
+extern "C" int lrs_dipnet_get_frame(const lrs_dipnet *net, int *top, int *left, int *H, int *W) {
+    if (!net) return LRS_E_INVALID;
+    if (top) *top = net->fr_top; if (left) *left = net->fr_left;
+    if (H) *H = net->fr_H; if (W) *W = net->fr_W;
+    return LRS_OK;
+}
+
 extern "C" const float *lrs_dipnet_output(const lrs_dipnet *net) {
     return (net && net->ws) ? net->f(net->nodes.back().out_off) : nullptr;
 }
@@ -941,8 +1017,10 @@ extern "C" int lrs_dipnet_train_steps_cmask(lrs_dipnet *net, const float *x, con
         return LRS_OK;
     }
     if (!st) return LRS_E_INVALID;   // capture needs a non-default stream
-    const lrs_dipnet::Key k{x, target, mask, es, ring, mstride, lr, beta1, beta2, eps};
-    static_assert(sizeof(lrs_dipnet::Key) == 5 * sizeof(void *) + sizeof(int64_t) + 4 * sizeof(float), "Key has padding");
+    const lrs_dipnet::Key k{x, target, mask, es, ring, mstride, lr, beta1, beta2, eps,
+                            net->fr_top, net->fr_left, net->fr_H, net->fr_W};
+    static_assert(sizeof(lrs_dipnet::Key) == 5 * sizeof(void *) + sizeof(int64_t) + 4 * sizeof(float) + 4 * sizeof(int32_t),
+                  "Key has padding");
     if (!net->have_key || memcmp(&k, &net->key, sizeof(k)) != 0) {
         drop_graph(net);
         hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
@@ -983,8 +1061,7 @@ extern "C" int lrs_dipnet_last_loss(lrs_dipnet *net, double *loss, void *stream)
     hipError_t e = hipMemcpyAsync(&acc, net->loss_acc(), sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    const auto &L = net->nodes.back();
-    *loss = acc / ((double)L.C * (double)L.P);
+    *loss = acc / (double)net->n_mean();
     return LRS_OK;
 }
 

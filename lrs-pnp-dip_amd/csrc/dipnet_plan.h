@@ -103,8 +103,18 @@ struct lrs_dipnet {
         const void *x, *t, *m, *es, *ring;
         int64_t mstride;   // the mask mode: [P] and [C][P] at one pointer are different graphs
         float lr, b1, b2, eps;
+        int32_t fr_top, fr_left, fr_H, fr_W;   // the frame (lrs_dipnet_set_frame): another loss mean and ring
     } key{};
     bool have_key = false;
+    // The image inside the output (lrs_dipnet_set_frame; the whole output until it is called:
+    // lrs_dipnet_create).  framed: the loss heads average over the interior's n_mean() elements and the
+    // early-stopping ring holds the interior only; not framed: the step is what it was without a frame.
+    int fr_top = 0, fr_left = 0, fr_H = 0, fr_W = 0;
+    bool framed = false;
+    int64_t n_mean() const {
+        const Node &L = nodes.back();
+        return framed ? (int64_t)L.C * fr_H * fr_W : (int64_t)L.C * L.P;
+    }
     lrs_dip_opts opts{};      // fixed at creation (precision, upsampled data-gradient form)
     float ln_lambda = 1.0f;   // W_used = W / max(1, sigma / ln_lambda)   (lipschitz_constraint_layer.py:42-44)
 

@@ -57,6 +57,9 @@ _lib = None
 _device_checked = False
 # the entry points that take a per-band mask [C][P] (the only ones a variant build may lack)
 _PER_BAND_MASK = ("lrs_masked_mse_cmask_f32", "lrs_dipnet_train_steps_cmask")
+# ... and the ones of the reflected frame (images of a size the DIP net does not reproduce)
+_FRAME = ("lrs_masked_mse_framed_f32", "lrs_unfolded_to_frame_f32", "lrs_frame_to_unfolded_f32",
+          "lrs_dipnet_set_frame", "lrs_dipnet_get_frame")
 
 
 def build(force: bool = False) -> str:
@@ -136,6 +139,11 @@ def _declare(L):
         "lrs_masked_mse_cmask_f32": (i32, [vp, vp, vp, i32, i32, i64, vp, vp, vp]),
         "lrs_unfolded_to_image_f32": (i32, [vp, vp, f32, i64, i64, i64, vp, vp]),
         "lrs_image_to_unfolded_f32": (i32, [vp, i64, i64, i64, vp, vp]),
+        "lrs_masked_mse_framed_f32": (i32, [vp, vp, vp, i32, i32, i64, i64, vp, vp, vp]),
+        "lrs_unfolded_to_frame_f32": (i32, [vp, vp, f32, i64, i64, i64, i64, i64, i64, i64, vp, vp]),
+        "lrs_frame_to_unfolded_f32": (i32, [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp]),
+        "lrs_dipnet_set_frame": (i32, [vp, i32, i32, i32, i32]),
+        "lrs_dipnet_get_frame": (i32, [vp] + [c.POINTER(c.c_int)] * 4),
         "lrs_es_ring_bytes": (sz, [i32, i64]),
         "lrs_es_init": (i32, [vp, i32, i32, vp]),
         "lrs_es_update_f32": (i32, [vp, i64, vp, vp, vp]),
@@ -164,8 +172,8 @@ def _declare(L):
         "lrs_stream_wait": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
-        if name in _PER_BAND_MASK and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
-            continue   # an A/B build from before the per-band masks: its [P] paths still time against this one
+        if name in _PER_BAND_MASK + _FRAME and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
+            continue   # an A/B build from before these: its other paths still time against this one
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

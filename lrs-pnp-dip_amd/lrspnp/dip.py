@@ -204,6 +204,16 @@ class DipNet:
             self.offsets.append(tuple(x.value for x in o))
         self.stream = torch.cuda.Stream(device=device, priority=int(stream_priority))
         self._es = None
+        self.frame = (0, 0) + self.out_shape[1:]    # (top, left, H, W): the whole output, no frame
+
+    def set_frame(self, top: int, left: int, H: int, W: int):
+        """The image inside the output (lrs_dipnet_set_frame): train_steps then averages the loss over its
+        C*H*W elements and feeds the early stopper its crop; the mask must be 0 outside it."""
+        rc = self.L.lrs_dipnet_set_frame(self.h, int(top), int(left), int(H), int(W))
+        if rc != 0:
+            raise _lib.LrsError(f"a {H}x{W} image at ({top}, {left}) is no frame inside the {self.out_shape[1]}x"
+                                f"{self.out_shape[2]} output: every reflected pad must be smaller than its dimension")
+        self.frame = (int(top), int(left), int(H), int(W))
 
     def __del__(self):
         try:
@@ -394,6 +404,9 @@ class DipConfig:
     use_graph: bool = False       # replay one captured hipGraph per step (measured slower than
                                   # direct launches on ROCm 7.2 for this ~110-kernel step)
     hidden: int = 128
+    # 'auto': an image of a size the net does not reproduce is trained inside the smallest reflected
+    # frame it does reproduce (frame_for); 'off': such a size is refused (the reference's behaviour)
+    frame: str = "auto"
     net: str = "unet1lip"         # 'unet1lip' (…1-LiP.py:214) or 'skip' (…pro.py:215-221)
     early_stop: bool = True       # False: exactly num_iter steps (the timed-benchmark mode, §8d)
 
@@ -408,21 +421,81 @@ class DipProx:
         self.cfg = cfg or DipConfig()
         nodes = (skip_nodes(bands, bands) if self.cfg.net == "skip"
                  else lipschitz_unet_nodes(bands, bands, self.cfg.hidden))
-        self.net = DipNet(nodes, bands, H, W, device=device, stream_priority=stream_priority)
-        if self.net.out_shape != (bands, H, W):
-            raise ValueError(f"the DIP net maps {H}x{W} to {self.net.out_shape[1:]}; the reference "
+        if self.cfg.frame not in ("auto", "off"):
+            raise ValueError(f"DipConfig.frame is 'auto' or 'off', not {self.cfg.frame!r}")
+        # the image's H x W at (top, left) of the Hf x Wf the net is built at (no frame: Hf, Wf = H, W)
+        Hf, Wf, top, left = frame_for(nodes, H, W) if self.cfg.frame == "auto" else (H, W, 0, 0)
+        self.H, self.W, self.Hf, self.Wf, self.top, self.left = H, W, Hf, Wf, top, left
+        self.framed = (Hf, Wf) != (H, W)
+        out_hw = net_out_hw(nodes, Hf, Wf)   # (on the host, before any device work)
+        if out_hw != (Hf, Wf):
+            raise ValueError(f"the DIP net maps {H}x{W} to {out_hw}; the reference "
                              "architecture needs sizes it reproduces (e.g. 36, 196 for the U-Net)")
-        self.es = EarlyStopper(bands * H * W, self.cfg.es_size, self.cfg.patience, device=device)
+        self.net = DipNet(nodes, bands, Hf, Wf, device=device, stream_priority=stream_priority)
+        if self.framed:
+            self.net.set_frame(top, left, H, W)
+        self.es = EarlyStopper(bands * H * W, self.cfg.es_size, self.cfg.patience, device=device)   # the image only
         self.calls = 0
         self.last_steps = 0
         self.last_stop_epoch = None
+        self.last_framed = None
+        self._mask_key = self._mask_framed = None
+
+    # ---- the frame ----------------------------------------------------------------------------
+    def crop(self, img):
+        """The image inside a framed (..., Hf, Wf) tensor (a view)."""
+        return img[..., self.top:self.top + self.H, self.left:self.left + self.W]
+
+    def _framed_image(self, t, what):
+        """target / input as the net takes it: (C, Hf, Wf) as it is, (C, H, W) reflected into the frame
+        (a copy: callers on a hot path write the framed tensor themselves, ops.unfolded_to_frame)."""
+        import torch
+        C = self.net.in_shape[0]
+        if t.numel() == C * self.Hf * self.Wf:
+            return t
+        if t.numel() != C * self.H * self.W:
+            raise _lib.LrsError(f"{what} has {t.numel()} elements ({tuple(t.shape)}): expected ({C}, {self.H}, {self.W})"
+                                f" or its frame ({C}, {self.Hf}, {self.Wf})")
+        pad = (self.left, self.Wf - self.W - self.left, self.top, self.Hf - self.H - self.top)
+        return torch.nn.functional.pad(t.reshape(1, C, self.H, self.W), pad, mode="reflect")[0].contiguous()
+
+    def _framed_mask(self, mask):
+        """The loss mask on the frame: the caller's (P,) / (H, W) / (C, H, W) mask inside, 0 outside; built
+        once per mask tensor (and again when that tensor is written).  A mask already of the frame's size
+        passes through: its frame must be 0."""
+        import torch
+        if mask is None:
+            mask = torch.ones(self.H * self.W, dtype=torch.float32, device=self.net.params.device)
+            key = None
+        else:
+            key = (mask.data_ptr(), tuple(mask.shape), mask._version)
+        C, P, Pf = self.net.out_shape[0], self.H * self.W, self.Hf * self.Wf
+        n = mask.numel()
+        if n not in (P, C * P):
+            if n in (Pf, C * Pf):
+                return mask
+            raise _lib.LrsError(f"mask has {n} elements ({tuple(mask.shape)}): expected a pixel mask ({P},) / "
+                                f"({self.H}, {self.W}) or a per-band mask ({C}, {self.H}, {self.W})")
+        if self._mask_framed is not None and key == self._mask_key:
+            return self._mask_framed
+        ch = n // P
+        m = torch.zeros((ch, self.Hf, self.Wf), dtype=torch.float32, device=mask.device)
+        self.crop(m).copy_(mask.reshape(ch, self.H, self.W))
+        self._mask_key, self._mask_framed = key, (m.reshape(-1) if ch == 1 else m)
+        return self._mask_framed
 
     def run(self, target, dip_input, mask, seed: int | None = None, num_iter: int | None = None,
             early_stop: bool = True):
         """Train a freshly initialised net on (dip_input -> target under mask) and return the output
-        at the early-stopping epoch (or after num_iter steps with early_stop=False).
+        at the early-stopping epoch (or after num_iter steps with early_stop=False), as (C, H, W).
         mask: (P,) / (H, W), one pixel mask for every band (the reference's mask_bkg), or (C, H, W),
         a mask per band (DipNet.train_steps).
+
+        An image of a size the net does not reproduce (cfg.frame = 'auto') is trained inside a reflected
+        frame: target, input and mask are still the image's (C, H, W); the loss, the early stopping and
+        the result cover the image only.  target / dip_input may also arrive framed, (C, Hf, Wf).  After a
+        fixed-step run last_framed is the engine's whole framed output (None otherwise): the result is
+        its crop, a strided view.
 
         The result is a view of an engine buffer, valid until the next call; it is ordered after
         the caller's current stream (the caller's stream waits for the DIP stream on return)."""
@@ -430,6 +503,10 @@ class DipProx:
         cfg = self.cfg
         n_iter = cfg.num_iter if num_iter is None else num_iter
         net = self.net
+        self.last_framed = None
+        if self.framed:
+            target, dip_input = self._framed_image(target, "target"), self._framed_image(dip_input, "dip_input")
+            mask = self._framed_mask(mask)
         net.mask_channels(mask)   # a mask of neither shape is refused before anything is enqueued
         stream_wait(net.stream, torch.cuda.current_stream())
         net.init_params(self.calls if seed is None else seed)
@@ -437,6 +514,9 @@ class DipProx:
         if not early_stop:
             net.train_steps(dip_input, target, mask, n_iter, cfg.learning_rate, use_graph=cfg.use_graph)
             self.last_steps, self.last_stop_epoch = n_iter, None
+            if self.framed:
+                self.last_framed = net.output()
+                return self.crop(self.last_framed)
             return net.output()                    # the last step's forward output (`out`)
         L = _lib.device_lib()
         _check(L.lrs_es_init(_ptr(self.es.state), cfg.es_size, cfg.patience, ctypes.c_void_p(net.stream.cuda_stream)),
@@ -452,12 +532,13 @@ class DipProx:
                 break
         stream_wait(torch.cuda.current_stream(), net.stream)
         self.last_steps = done
+        shape = (net.out_shape[0], self.H, self.W)   # the ring holds the image, framed or not
         if st is not None and st.stop:
             self.last_stop_epoch = st.stop_epoch
-            return self.es.slot_of(st.stop_epoch).view(net.out_shape)
+            return self.es.slot_of(st.stop_epoch).view(shape)
         # the reference returns None here (its loop ends without returning); use the last output
         self.last_stop_epoch = None
-        return self.es.slot_of(st.count - 1).view(net.out_shape)
+        return self.es.slot_of(st.count - 1).view(shape)
 
 
     def steps_to_possible_stop(self, st) -> int:
@@ -521,6 +602,53 @@ def unet_size_ok(H: int, W: int) -> bool:
     return (h, w) == (H, W)
 
 
+def net_out_hw(nodes, H: int, W: int):
+    """(Ho, Wo) the node list maps an H x W input to, by the engine's own host-side shape logic
+    (lrs_dipnet_create needs no device); None where it refuses the size."""
+    L = _lib.lib()
+    arr = (DipNode * len(nodes))(*nodes)
+    h = ctypes.c_void_p()
+    opts = _lib.dip_opts()
+    if L.lrs_dipnet_create(arr, len(nodes), 1, int(H), int(W), ctypes.byref(opts), ctypes.byref(h)) != 0:
+        return None
+    try:
+        c, ho, wo = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        L.lrs_dipnet_out_shape(h, ctypes.byref(c), ctypes.byref(ho), ctypes.byref(wo))
+        return ho.value, wo.value
+    finally:
+        L.lrs_dipnet_destroy(h)
+
+
+FRAME_SEARCH = 32   # frame_for gives up after this many sizes above the image's
+
+
+def frame_for(nodes, H: int, W: int):
+    """(Hf, Wf, top, left): the smallest Hf >= H, Wf >= W the node list maps back to themselves, and
+    where the image sits in that frame, top = (Hf - H) // 2, left = (Wf - W) // 2.  Host only.  For
+    lipschitz_unet_nodes Hf = 16 ceil((H + 12) / 16) - 12.  ValueError when no size up to +32 fits, or
+    when a pad reaches the dimension it reflects (nn.ReflectionPad2d's rule: pad < size)."""
+    def fit(n):   # on a square probe: a size the net refuses along the other axis says nothing about this one
+        for f in range(n, n + FRAME_SEARCH + 1):
+            if net_out_hw(nodes, f, f) == (f, f):
+                return f
+        raise ValueError(f"the DIP net reproduces no size from {n} to {n + FRAME_SEARCH}")
+
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"image size {H}x{W}")
+    Hf = fit(H)
+    Wf = Hf if W == H else fit(W)
+    if net_out_hw(nodes, Hf, Wf) != (Hf, Wf):
+        raise ValueError(f"the DIP net does not reproduce {Hf}x{Wf}, the frame found for {H}x{W}")
+    top, left = (Hf - H) // 2, (Wf - W) // 2
+    for n, lo, f in ((H, top, Hf), (W, left, Wf)):
+        if max(lo, f - n - lo) >= n:
+            raise ValueError(f"a {H}x{W} image needs the {Hf}x{Wf} frame, whose pad of {max(lo, f - n - lo)} "
+                             f"reaches the dimension of {n} it reflects")
+    return Hf, Wf, top, left
+
+
 __all__ = ["DipNode", "DipNet", "EarlyStopper", "DipConfig", "DipProx", "LipschitzDip", "lipschitz_unet_nodes",
            "lipschitz_unet_units", "skip_nodes",
-           "UNET_REF_NAMES", "dip_input_from_unfolded", "unfolded_from_image", "sigma_max", "unet_size_ok"]
+           "UNET_REF_NAMES", "dip_input_from_unfolded", "unfolded_from_image", "sigma_max", "unet_size_ok",
+           "frame_for", "net_out_hw"]

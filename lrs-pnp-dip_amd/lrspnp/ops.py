@@ -15,7 +15,7 @@ from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLA
                    SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, LrsError, check, device_lib, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "masked_mse", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -436,6 +436,37 @@ def image_to_unfolded(img, H: int, W: int, out=None, stream=None):
     return out
 
 
+def unfolded_to_frame(X, L, c: float, H: int, W: int, top: int, left: int, Hf: int, Wf: int, out=None, stream=None):
+    """unfolded_to_image into rows top.., columns left.. of a (B, Hf, Wf) image whose frame is filled by
+    reflection without repeating the edge (nn.ReflectionPad2d), in one pass (lrs_unfolded_to_frame_f32)."""
+    Ld = device_lib()
+    _dev(X, torch.float32, "X")
+    P, B = X.shape
+    if P != H * W:
+        raise LrsError(f"P = {P} != H*W = {H * W}")
+    out = out if out is not None else torch.empty((B, Hf, Wf), dtype=torch.float32, device=X.device)
+    if out.numel() != B * Hf * Wf:
+        raise LrsError(f"out has {out.numel()} elements, not {B}x{Hf}x{Wf}")
+    check(Ld.lrs_unfolded_to_frame_f32(_p(X), _p(L), ctypes.c_float(c), H, W, B, top, left, Hf, Wf, _p(out),
+                                       _s(stream)), "lrs_unfolded_to_frame_f32")
+    return out
+
+
+def frame_to_unfolded(img, H: int, W: int, top: int, left: int, out=None, stream=None):
+    """image_to_unfolded of the H x W image at (top, left) of the framed (B, Hf, Wf) img."""
+    Ld = device_lib()
+    _dev(img, torch.float32, "img")
+    if img.dim() != 3:
+        raise LrsError(f"img {tuple(img.shape)} must be (B, Hf, Wf)")
+    B, Hf, Wf = img.shape
+    out = out if out is not None else torch.empty((H * W, B), dtype=torch.float32, device=img.device)
+    if out.numel() != H * W * B:
+        raise LrsError(f"out has {out.numel()} elements, not {H * W}x{B}")
+    check(Ld.lrs_frame_to_unfolded_f32(_p(img), H, W, B, top, left, Hf, Wf, _p(out), _s(stream)),
+          "lrs_frame_to_unfolded_f32")
+    return out
+
+
 def mask_channels(mask, C: int, P: int) -> int:
     """The mode of a DIP loss mask for a C x P output: 1 for a pixel mask (P elements, applied to every
     channel), C for a per-element mask (C*P elements, the layout of the output: a mask that differs
@@ -451,9 +482,11 @@ def mask_channels(mask, C: int, P: int) -> int:
                    f"{P} or a per-band mask (C, H, W) with {C * P}")
 
 
-def masked_mse(out, target, mask=None, want_grad: bool = True, stream=None):
+def masked_mse(out, target, mask=None, want_grad: bool = True, stream=None, n_mean: int | None = None):
     """MSELoss(target*mask, out*mask) over the C x P elements of out (C, ...) and its gradient dL/dout
     (…1-LiP.py:234).  mask: None, P elements (every channel) or C*P elements (per band).
+    n_mean: out holds its image inside a frame on which the mask is 0; the mean is over the image's n_mean
+    elements instead of C*P (lrs_masked_mse_framed_f32).
     Returns (loss: float64 device scalar, gout or None)."""
     Ld = device_lib()
     _dev(out, torch.float32, "out")
@@ -468,6 +501,10 @@ def masked_mse(out, target, mask=None, want_grad: bool = True, stream=None):
     gout = torch.empty_like(out) if want_grad else None
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         acc = torch.zeros(1, dtype=torch.float64, device=out.device)   # the kernel accumulates the sum
-        check(Ld.lrs_masked_mse_cmask_f32(_p(out), _p(target), _p(mask), mc, C, P, _p(gout), _p(acc), _s(stream)),
-              "lrs_masked_mse_cmask_f32")
-        return acc / (C * P), gout
+        if n_mean is None:
+            check(Ld.lrs_masked_mse_cmask_f32(_p(out), _p(target), _p(mask), mc, C, P, _p(gout), _p(acc), _s(stream)),
+                  "lrs_masked_mse_cmask_f32")
+            return acc / (C * P), gout
+        check(Ld.lrs_masked_mse_framed_f32(_p(out), _p(target), _p(mask), mc, C, P, int(n_mean), _p(gout), _p(acc),
+                                           _s(stream)), "lrs_masked_mse_framed_f32")
+        return acc / int(n_mean), gout

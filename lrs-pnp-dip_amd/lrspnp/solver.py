@@ -241,17 +241,34 @@ class LrsPnP:
     def _init_dip(self, image_shape, dev, engine=True):
         """DIP target = the observed cube as an image, mask_bkg = the pixel mask
         (…1-LiP.py:275-301); the network is re-initialised every outer iteration (:214)."""
-        from .dip import DipConfig, LipschitzDip
+        from .dip import DipConfig, LipschitzDip, frame_for, lipschitz_unet_nodes, skip_nodes
         if image_shape is None:
             raise LrsError("lowrank='dip' needs image_shape=(H, W) with H*W = P")
         H, W = (int(v) for v in image_shape)
         if H * W != self.P:
             raise LrsError(f"image_shape {H}x{W} does not match P = {self.P}")
         self.H, self.W = H, W
-        self.dip = LipschitzDip(self.B, H, W, self.cfg.dip or DipConfig(), device=dev,
+        dcfg = self.cfg.dip or DipConfig()
+        self.dip = LipschitzDip(self.B, H, W, dcfg, device=dev,
                                  stream_priority=self.cfg.lowrank_priority) if engine else None
-        self.dip_target = torch.empty((self.B, H, W), dtype=torch.float32, device=dev)
-        ops.unfolded_to_image(self.Y, None, 1.0, H, W, self.dip_target)
+        # An image of a size the net does not reproduce lives inside a reflected frame (dip.frame_for): the
+        # target and the net input are written framed, (B, Hf, Wf); the mask stays the image's (DipProx
+        # frames it once, zeros outside).  Without an engine (a DipTaskSplit worker) the frame is still
+        # worked out on the host, so every rank holds the same buffers.
+        if self.dip is not None:
+            self.frame = (self.dip.Hf, self.dip.Wf, self.dip.top, self.dip.left)
+        elif dcfg.frame == "auto":
+            self.frame = frame_for(skip_nodes(self.B, self.B) if dcfg.net == "skip"
+                                   else lipschitz_unet_nodes(self.B, self.B, dcfg.hidden), H, W)
+        else:
+            self.frame = (H, W, 0, 0)
+        Hf, Wf, top, left = self.frame
+        self.framed = (Hf, Wf) != (H, W)
+        self.dip_target = torch.empty((self.B, Hf, Wf), dtype=torch.float32, device=dev)
+        if self.framed:
+            ops.unfolded_to_frame(self.Y, None, 1.0, H, W, top, left, Hf, Wf, self.dip_target)
+        else:
+            ops.unfolded_to_image(self.Y, None, 1.0, H, W, self.dip_target)
         # The reference's mask_bkg is one (1,1,H,W) pixel mask.  A mask M that differs between bands
         # (dead columns, dropped lines, missing bands) goes to the loss per element instead, as
         # (B, H, W): the mask the caller passed is the specification (one device check, here only).
@@ -310,11 +327,19 @@ class LrsPnP:
 
     def low_rank_dip(self, stream):
         """U = DIP(X + L2/mu2) (…1-LiP.py:399-411) on `stream`; the host polls early stopping."""
-        ops.unfolded_to_image(self.X, self.L2, self.c2, self.H, self.W, self.dip_in, stream=stream)
+        Hf, Wf, top, left = self.frame
+        if self.framed:
+            ops.unfolded_to_frame(self.X, self.L2, self.c2, self.H, self.W, top, left, Hf, Wf, self.dip_in,
+                                  stream=stream)
+        else:
+            ops.unfolded_to_image(self.X, self.L2, self.c2, self.H, self.W, self.dip_in, stream=stream)
         with torch.cuda.stream(stream):
             img = self.dip.run(self.dip_target, self.dip_in, self.dip_mask, seed=self.cfg.dip_seed + self.iteration,
                                early_stop=self.dip.cfg.early_stop)
-            ops.image_to_unfolded(img, self.H, self.W, self.U, stream=stream)
+            if self.dip.last_framed is not None:   # a fixed-step run inside a frame: the image out of the framed output
+                ops.frame_to_unfolded(self.dip.last_framed, self.H, self.W, top, left, self.U, stream=stream)
+            else:
+                ops.image_to_unfolded(img, self.H, self.W, self.U, stream=stream)
         self.dip_steps.append((self.dip.last_steps, self.dip.last_stop_epoch))
 
     def step(self):

@@ -3,6 +3,7 @@
 `--steps` steps; prints each round and the median.
 
     python tools/dip_steptime.py [--hw 196] [--bands 198] [--steps 100] [--rounds 7] [--graph]
+    python tools/dip_steptime.py --hw 212 --frame 200     # a 200x200 image inside the 212x212 frame
 """
 import argparse
 import os
@@ -29,6 +30,9 @@ ap.add_argument("--dump", default=None, help="also save the net output after the
                                               "bit-for-bit A/B of output-preserving kernel changes")
 ap.add_argument("--bandmask", action="store_true", help="a band-varying mask (lrspnp.data.stripe_mask, (bands, hw, "
                                                          "hw)): the loss heads' per-element [C][P] mode")
+ap.add_argument("--frame", type=int, default=0, help="the side of an image centred inside the hw x hw net "
+                                                     "(lrs_dipnet_set_frame: the loss and the early stopping on "
+                                                     "the image alone, the mask 0 on the frame); 0: no frame")
 a = ap.parse_args()
 nodes = lipschitz_unet_nodes(a.bands, a.bands, 128) if a.net == "unet" else skip_nodes(a.bands, a.bands)
 net = DipNet(nodes, a.bands, a.hw, a.hw, stream_priority=a.priority)
@@ -40,10 +44,17 @@ m = (torch.rand(a.hw, a.hw, device="cuda", generator=g) > 0.2).float()
 if a.bandmask:
     from lrspnp.data import stripe_mask
     m = torch.from_numpy(stripe_mask(a.hw, a.hw, a.bands, 0)).cuda()
+inner = a.frame or a.hw
+if a.frame:
+    top = (a.hw - a.frame) // 2
+    net.set_frame(top, top, a.frame, a.frame)
+    inside = torch.zeros_like(m)
+    inside[..., top:top + a.frame, top:top + a.frame] = 1.0
+    m = m * inside
 es = None
 if a.es:
     from lrspnp.dip import EarlyStopper
-    es = EarlyStopper(a.bands * a.hw * a.hw, 30, 10 ** 6)   # never stops: every step runs the full test
+    es = EarlyStopper(a.bands * inner * inner, 30, 10 ** 6)   # never stops: every step runs the full test
 net.train_steps(x, t, m, 10, use_graph=a.graph, es=es)
 torch.cuda.synchronize()
 res = []
