@@ -16,6 +16,7 @@
 
 #include "dip_gemm.h"
 #include "dip_kernels.h"
+#include "dip_bn.h"
 
 namespace lrs {
 
@@ -165,7 +166,8 @@ __global__ __launch_bounds__(kDirTh) void k_conv_bn_dir(const float *__restrict_
         if (bias) z = z + bc;
         return z;
     };
-    // k_reduce_bn1's BatchNorm (bn_fwd_finish's arithmetic) from here on
+    // k_reduce_bn1's BatchNorm from here on: bn_fwd_stat's arithmetic (dip_bn.h) and stores on the running statistics
+    // fetched above (calling it instead changed this kernel's instruction stream), then bn_norm_act
     float zv[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(kDirTh) void k_conv_bn_dir(const float *__restrict_
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int i = t + u * kDirTh;
-        if (i < P) a.y[zoff + i] = act_fwd((zv[u] - m32) * is32 * gm + bt, a.act);
+        if (i < P) a.y[zoff + i] = bn_norm_act(zv[u], m32, is32, gm, bt, a.act);
     }
 }
 

@@ -1,5 +1,6 @@
 // DIP low-rank prox, host side: conv geometry, tile and split-K choice, and the launchers of the
-// kernels in dip_kernels.h / dip_gemm.h / dip_sm.h / dip_dir.h.  Part of dipnet.hip's translation
+// kernels in dip_kernels.h / dip_bn.h / dip_sn.h / dip_train.h / dip_gemm.h / dip_sm.h / dip_dir.h
+// (BatchNorm's form pickers and template dispatch are dip_bn.h's own).  Part of dipnet.hip's translation
 // unit (its only includer): the kernels defined here keep their internal linkage.
 #pragma once
 #include <math.h>
@@ -10,6 +11,9 @@
 #include <vector>
 
 #include "dip_kernels.h"
+#include "dip_bn.h"
+#include "dip_sn.h"
+#include "dip_train.h"
 #include "dip_gemm.h"
 #include "dip_sm.h"
 #include "dip_dir.h"
@@ -642,52 +646,10 @@ int conv_bwd(const ConvGeom &g, const float *gz, const float *col, const float *
     return LRS_OK;
 }
 
-// workgroups per channel for the BN kernels: ~4096 elements each, at most 64
-inline int bn_split(int64_t P) {
-    int64_t S = (P + 4095) / 4096;
-    if (S < 1) S = 1;
-    if (S > 64) S = 64;
-    return (int)S;
-}
-
-inline int64_t bn_part_doubles(int C, int64_t P) { return (int64_t)C * bn_split(P) * 3; }
-
-// a BatchNorm channel that fits one workgroup: k_reduce_bn1 / k_reduce_bn_bwd1 can finish a pending
-// split-K sum themselves
-inline bool bn_one_wg(int64_t P) { return P <= 4 * kBn1Threads && bn_split(P) == 1; }
-
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-// Register-resident one-workgroup-per-channel BN (k_bn_fwd_r / k_bn_bwd_r): float4 quads per
-// thread for a channel of P pixels, or 0 where the S-way split / the P <= 4096 kernels are used.
-inline int bn_reg_q(int64_t P, bool vec) {
-    if (!vec || P <= 4 * kBn1Threads || P > (int64_t)4 * kBn1Threads * kBnRegMaxQ) return 0;
-    const int q = (int)((P + 4 * kBn1Threads - 1) / (4 * kBn1Threads));
-    static const int qs[] = {2, 3, 4, 6, 8, 10};
-    for (int v : qs)
-        if (v >= q) return v;
-    return 0;
-}
-
-// Threads of a one-workgroup-per-channel BatchNorm kernel (k_reduce_bn1, k_reduce_bn_bwd1, k_bn_fwd1,
-// k_bn_bwd1): kBn1Small where the channel fits 2 values per thread of it (the 18^2 and smaller maps at
-// 36^2, the 13^2 ones at 196^2), else kBn1Threads.  A/B (2 interleaved rounds): 36^2 step 0.671 ->
-// 0.657 ms with 256 threads up to 1024 pixels, but the 196^2 step 1.274 -> 1.280 (its 25^2 maps then
-// hold 3 values per thread).  (A kBn1Small-thread kernel covers at most 4 values per thread.)
-constexpr int64_t kBn1SmallMaxP = 2 * kBn1Small;
-static_assert(kBn1SmallMaxP <= 4 * kBn1Small, "a kBn1Small-thread kernel holds 4 values per thread");
-inline int bn1_threads(int64_t P) { return P <= kBn1SmallMaxP ? kBn1Small : kBn1Threads; }
-
-#define LRS_BNR_SWITCH(nq, K, ...)                                                                \
-    switch (nq) {                                                                                 \
-    case 2: hipLaunchKernelGGL(K<2>, __VA_ARGS__); break;                                         \
-    case 3: hipLaunchKernelGGL(K<3>, __VA_ARGS__); break;                                         \
-    case 4: hipLaunchKernelGGL(K<4>, __VA_ARGS__); break;                                         \
-    case 6: hipLaunchKernelGGL(K<6>, __VA_ARGS__); break;                                         \
-    case 8: hipLaunchKernelGGL(K<8>, __VA_ARGS__); break;                                         \
-    default: hipLaunchKernelGGL(K<10>, __VA_ARGS__); break;                                       \
-    }
-
+// BatchNorm (+ activation) of z as stored, forward and backward: the form from dip_bn.h's pickers
+// (register resident, one workgroup per channel, or the S-way split; without gamma the activation alone)
 int bn_fwd(const float *z, float *y, const float *gamma, const float *beta, float *mean, float *invstd, float *rm,
            float *rv, int C, int64_t P, int act, float eps, float mom, double *part, hipStream_t st, int lip = 1) {
     const int S = bn_split(P);
@@ -697,9 +659,8 @@ int bn_fwd(const float *z, float *y, const float *gamma, const float *beta, floa
     BnArgs a{z, y, gamma, beta, mean, invstd, rm, rv, part, C, (int)P, S, chunk, gamma ? 1 : 0, act, eps, mom, lip,
              vec};
     if (const int nq = gamma ? bn_reg_q(P, vec) : 0) {
-        LRS_BNR_SWITCH(nq, k_bn_fwd_r, dim3(1, C), dim3(kBn1Threads), 0, st, (const float *)nullptr, 0,
-                       (const float *)nullptr, a);
-    } else if (gamma && S == 1) {
+        launch_bn_fwd_r(nq, nullptr, 0, nullptr, a, nullptr, st);
+    } else if (gamma && bn_one_wg(P)) {
         hipLaunchKernelGGL(k_bn_fwd1, dim3(1, C), dim3(bn1_threads(P)), 0, st, a);
     } else {
         if (gamma) hipLaunchKernelGGL(k_bn_stats, dim3(S, C), dim3(kBnThreads), 0, st, a);
@@ -719,8 +680,8 @@ int bn_bwd(const float *gy, const float *y, const float *z, const float *gamma, 
     BnBwdArgs a{gy, y, z, gamma, mean, invstd, gz, ggamma, gbeta, gbias, part, C, (int)P, S, chunk,
                 gamma ? 1 : 0, act, lip, accum, vec, gamma ? beta : nullptr};
     if (const int nq = gamma ? bn_reg_q(P, vec) : 0) {
-        LRS_BNR_SWITCH(nq, k_bn_bwd_r, dim3(1, C), dim3(kBn1Threads), 0, st, a);
-    } else if ((gamma || gbias) && S == 1) {
+        launch_bn_bwd_r(nq, a, st);
+    } else if ((gamma || gbias) && bn_one_wg(P)) {
         hipLaunchKernelGGL(k_bn_bwd1, dim3(1, C), dim3(bn1_threads(P)), 0, st, a);
     } else {
         if (gamma || gbias) hipLaunchKernelGGL(k_bn_bwd_stats, dim3(S, C), dim3(kBnThreads), 0, st, a);

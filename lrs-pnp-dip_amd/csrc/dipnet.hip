@@ -413,15 +413,9 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
             }
             const float *pp = nsplit > 1 ? (const float *)part : nullptr;
             if (pl.bn == BnFwd::Reg) {
-                LRS_BNR_SWITCH(pl.nq, k_bn_fwd_r, dim3(1, N.C), dim3(kBn1Threads), 0, st, pp, nsplit, bias,
-                               net->bn_args(N, 1), sdiv);
+                launch_bn_fwd_r(pl.nq, pp, nsplit, bias, net->bn_args(N, 1), sdiv, st);
             } else if (pl.bn == BnFwd::Reduce1 && nsplit > 1) {
-                if (bn1_threads(N.P) == kBn1Small)
-                    hipLaunchKernelGGL(k_reduce_bn1<kBn1Small>, dim3(1, N.C), dim3(kBn1Small), 0, st, pp, nsplit, bias,
-                                       net->bn_args(N, 0), sdiv);
-                else
-                    hipLaunchKernelGGL(k_reduce_bn1<kBn1Threads>, dim3(1, N.C), dim3(kBn1Threads), 0, st, pp, nsplit, bias,
-                                       net->bn_args(N, 0), sdiv);
+                launch_reduce_bn1(pp, nsplit, bias, net->bn_args(N, 0), sdiv, st);
             } else if (pl.bn == BnFwd::Reduce1 || pl.bn == BnFwd::Generic) {
                 rc = bn_fwd(z, out, bn ? net->params + N.gm_off : nullptr, bn ? net->params + N.bt_off : nullptr,
                             net->f(N.mean_off), net->f(N.istd_off), bn ? net->bnstats + N.rs_off : nullptr,
@@ -554,7 +548,7 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
         return weight_grad(net, j, x, net->side, net->f(net->part2_off));
     };
     // a small-map data gradient may leave dL/dy of the next node as split-K partials, finished by
-    // that node's k_reduce_bn_bwd1 (pend = the partials, pend_S their count)
+    // that node's BatchNorm backward (launch_reduce_bn_bwd1; pend = the partials, pend_S their count)
     const float *pend = nullptr;
     int pend_S = 0;
     for (int i = n - 1; i >= 0; --i) {
@@ -568,11 +562,7 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
             float *z = bn ? net->f(N.z_off) : outp;
             float *gz = net->f(N.gz_off);
             if (pend) {
-                const BnBwdArgs a = net->bn_bwd_args(N);
-                if (bn1_threads(N.P) == kBn1Small)
-                    hipLaunchKernelGGL(k_reduce_bn_bwd1<kBn1Small>, dim3(1, N.C), dim3(kBn1Small), 0, st, pend, pend_S, a);
-                else
-                    hipLaunchKernelGGL(k_reduce_bn_bwd1<kBn1Threads>, dim3(1, N.C), dim3(kBn1Threads), 0, st, pend, pend_S, a);
+                launch_reduce_bn_bwd1(pend, pend_S, net->bn_bwd_args(N), st);
                 pend = nullptr;
             } else if (!(head_done && i == n - 1)) {   // else k_mse_head wrote gz and the bias gradient
                 rc = bn_bwd(gout, outp, z, bn ? net->params + N.gm_off : nullptr, net->f(N.mean_off),

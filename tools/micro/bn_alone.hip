@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "dip_kernels.h"
+#include "dip_bn.h"
 
 using namespace lrs;
 
@@ -81,13 +81,13 @@ int main() {
         const int P = 9604, S = 6;
         BnArgs a{z, y, g, bt, m, is, rm, rv, nullptr, C, P, 1, P, 1, LRS_ACT_LRELU, 1e-5f, 0.1f, 1, 1};
         printf("k_bn_fwd_r<3>, 98^2, %d partials: %6.2f us\n", S,
-               timeit([&]() { hipLaunchKernelGGL((k_bn_fwd_r<3, 1024>), dim3(1, C), dim3(1024), 0, 0, (const float *)part, S, (const float *)bias, a, (const float *)nullptr); }, 500));
+               timeit([&]() { hipLaunchKernelGGL(k_bn_fwd_r<3>, dim3(1, C), dim3(1024), 0, 0, (const float *)part, S, (const float *)bias, a, (const float *)nullptr); }, 500));
     }
     {
         const int P = 38416;
         BnArgs a{z, y, g, bt, m, is, rm, rv, nullptr, C, P, 1, P, 1, LRS_ACT_LRELU, 1e-5f, 0.1f, 1, 1};
         printf("k_bn_fwd_r<10>, 196^2, z given: %6.2f us\n",
-               timeit([&]() { hipLaunchKernelGGL((k_bn_fwd_r<10, 1024>), dim3(1, C), dim3(1024), 0, 0, (const float *)nullptr, 1, (const float *)bias, a, (const float *)nullptr); }, 500));
+               timeit([&]() { hipLaunchKernelGGL(k_bn_fwd_r<10>, dim3(1, C), dim3(1024), 0, 0, (const float *)nullptr, 1, (const float *)bias, a, (const float *)nullptr); }, 500));
     }
     return 0;
 }
