@@ -360,8 +360,10 @@ int lrs_conv_bn_small_f32(const float *x, int Cin, int H, int W, const float *w,
                           float *run_mean, float *run_var, void *stream);
 
 /* sigma_max of n weight matrices W[i] (rows[i] x cols[i], min(rows, cols) <= 128; host arrays
- * of device pointers), exact to fp64 before the float32 rounding; scale = max(1, sigma/ln_lambda)
- * and, when Wn != NULL, Wn[i] = W[i] / scale[i]. */
+ * of device pointers), within 1 float32 ulp of the fp64 SVD value for 5e-20 < sigma < 1e19, unless the
+ * top singular vector's component along the Lanczos start vector is below c(g) for the relative gap g
+ * to sigma_2 (3e-8 at g = 1e-3 ... 3e-4 at g = 1e-6, csrc/dip_sn.h); sigma is then low by at most the
+ * gap, never high.  scale = max(1, sigma/ln_lambda) and, when Wn != NULL, Wn[i] = W[i] / scale[i]. */
 size_t lrs_sigma_max_workspace(int n);
 int lrs_sigma_max_f32(const float *const *W, float *const *Wn, const int *rows, const int *cols, int n,
                       float ln_lambda, float *sigma, float *scale, void *ws, size_t ws_bytes,

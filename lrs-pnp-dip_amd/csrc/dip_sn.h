@@ -132,7 +132,17 @@ __global__ __launch_bounds__(256) void k_sn_gram_reduce(const SnConv *convs, dou
 // number of eigenvalues of the symmetric tridiagonal T_n above x, T_n given as ab[i] = {alpha_i,
 // beta_{i-1}^2}: n minus the sign changes of the characteristic-polynomial sequence p_i =
 // (alpha_i - x) p_{i-1} - beta_{i-1}^2 p_{i-2} (division-free; rescaled by a power of two every 4
-// terms, which changes no sign).
+// terms, which changes no sign).  The sequence starts from p_0 = s0, p_1 = (alpha_0 - x) s0 with s0 =
+// sn_scale(top of the round's grid) instead of p_0 = 1: at most 8 unscaled factors then stand between two
+// rescalings, the first included (with p_0 = 1 the first rescaling came after 9, which overflowed
+// for lambda_max above 1e34 and underflowed to an exact zero below 1e-36).  Signs are the same.
+__device__ __forceinline__ double sn_scale(double top) {
+    int e;
+    const double f = frexp(top, &e);
+    (void)f;
+    return (top > 0.0 && top < 1e300) ? ldexp(1.0, -e) : 1.0;
+}
+
 __device__ __forceinline__ void sturm_term(double a, double b2, double x, double &p, double &pm, int &changes) {
     double pn = __fma_rn(a - x, p, -b2 * pm);
     // a zero takes the sign opposite to its predecessor: perturb it to -p * 2^-600 (the usual
@@ -143,9 +153,9 @@ __device__ __forceinline__ void sturm_term(double a, double b2, double x, double
     p = pn;
 }
 
-__device__ __noinline__ int sturm_gt_checked(const double2 *ab, int n, double x) {
-    double pm = 1.0, p = ab[0].x - x;
-    p = p != 0.0 ? p : -0x1p-600;              // p_0 = 1 > 0: a zero p_1 counts as negative
+__device__ __noinline__ int sturm_gt_checked(const double2 *ab, int n, double x, double s0) {
+    double pm = s0, p = (ab[0].x - x) * s0;
+    p = p != 0.0 ? p : -s0 * 0x1p-600;         // p_0 = s0 > 0: a zero p_1 counts as negative
     int changes = p < 0.0;
     int i = 1;
     double2 c[4];
@@ -173,9 +183,9 @@ __device__ __noinline__ int sturm_gt_checked(const double2 *ab, int n, double x)
 // re-evaluated by sturm_gt_checked.  Without a zero both evaluate the same values (the power-of-
 // two rescaling, here every 8 terms, is exact), so the count is the checked one.  Eight terms'
 // LDS reads are in flight while eight are evaluated.
-__device__ __forceinline__ int sturm_gt(const double2 *ab, int n, double x) {
-    double pm = 1.0, p = ab[0].x - x;
-    if (p == 0.0) return sturm_gt_checked(ab, n, x);
+__device__ __forceinline__ int sturm_gt(const double2 *ab, int n, double x, double s0) {
+    double pm = s0, p = (ab[0].x - x) * s0;
+    if (p == 0.0) return sturm_gt_checked(ab, n, x, s0);
     int changes = p < 0.0;
     bool zero = false;
     int i = 1;
@@ -209,7 +219,7 @@ __device__ __forceinline__ int sturm_gt(const double2 *ab, int n, double x) {
         pm = p;
         p = pn;
     }
-    return zero ? sturm_gt_checked(ab, n, x) : n - changes;
+    return zero ? sturm_gt_checked(ab, n, x, s0) : n - changes;
 }
 
 // One 256-point multisection round on T_n: thread t tests x_t = base + step (t + 1); returns (to
@@ -235,7 +245,8 @@ __device__ __forceinline__ int sn_round(const double2 *ab, int n, double base, d
     if (t == 0) best[(rnd + 1) % 3] = -1;
     // the wave's largest flagged t by DPP, then one LDS atomic per wave (a per-lane atomicMax
     // compiled to a scalar loop over the flagged lanes)
-    const int wmax = wave_max_i(sturm_gt(ab, n, sn_grid(base, step, t)) >= 1 ? t : -1);
+    const double s0 = sn_scale(sn_grid(base, step, 255));
+    const int wmax = wave_max_i(sturm_gt(ab, n, sn_grid(base, step, t), s0) >= 1 ? t : -1);
     if ((t & 63) == 0 && wmax >= 0) atomicMax(slot, wmax);
     __syncthreads();
     const int bt = *slot;
@@ -266,6 +277,11 @@ __device__ __forceinline__ void sn_multisect(const double2 *ab, int n, double &l
 // with k, Cauchy interlacing).  Converged when it stayed in its cell for 4 steps (typically 28-40
 // steps for these weights instead of m = 128); one more round then narrows the cell 257x.
 // A move of more than 256 cells re-brackets from the Gershgorin bound.
+// Guarantee (tests/test_gpu_sigma.py): sigma is within 1 float32 ulp of the fp64 SVD
+// value for 5e-20 < sigma < 1e19, unless the top singular vector's component c along the start
+// vector is below c(g) for the relative gap g to sigma_2 (c(1e-3) = 3e-8, c(1e-4) = 1e-6, c(1e-5) =
+// 3e-5, c(1e-6) = 3e-4; none for g >= 1e-2): the top Ritz value then rests on sigma_2 for 4 steps, the
+// rule takes it for converged, and sigma is low by at most the gap (never high).
 // sigma32 = float(sqrt(lambda_max)); scale = max(1, sigma32 / ln_lambda) (float32, as torch).
 __global__ __launch_bounds__(256) void k_sn_sigma(const SnConv *convs, const double *gram, float *sigma,
                                                   float *scale, float ln_lambda, long long *prof) {

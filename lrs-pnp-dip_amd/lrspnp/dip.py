@@ -2,7 +2,7 @@
 
 Reference (shuoli0708/LRS-PnP-DIP):
   models/my_Lipschitz_Unet.py:21-148           my_Lipschitz_Unet (conv / bn / act stack)
-  models/lipschitz_constraint_layer.py:36-44   SpectralNorm (exact sigma_max, W_bar / max(1, sigma))
+  models/lipschitz_constraint_layer.py:36-44   SpectralNorm (sigma_max from the fp64 Gram, W_bar / max(1, sigma))
   lipschitz_constraint_layer.py:65-78          conv(): ReflectionPad2d((k-1)//2) + Conv2d(pad 0),
                                                kaiming_uniform_(a=0, fan_in)
   lipschitz_constraint_layer.py:88-122         BatchNormSpectralNorm (gamma/c, beta/c)
@@ -11,7 +11,7 @@ Reference (shuoli0708/LRS-PnP-DIP):
   main_LRS_PnP_DIP_1-LiP.py:404-411            DIP_input / U layout transforms
 
 Every layer runs in liblrspnp_hip.so (lrs_dipnet_*): explicit im2col + MFMA GEMMs, fused
-BN + LeakyReLU, an exact fp64 sigma_max per conv, Adam, the masked MSE and the early-stopping
+BN + LeakyReLU, an fp64 sigma_max per conv (1 float32 ulp, csrc/dip_sn.h), Adam, the masked MSE and the early-stopping
 test, all on device; one training step is optionally a single hipGraph launch.  There is no
 PyTorch compute here: torch only allocates the device buffers.
 """
@@ -569,7 +569,8 @@ def unfolded_from_image(img):
 
 
 def sigma_max(weights, ln_lambda: float = 1.0):
-    """sigma_max of each [rows, ...] weight tensor (lrs_sigma_max_f32); returns (sigma, scale)."""
+    """sigma_max of each [rows, ...] weight tensor (lrs_sigma_max_f32); returns (sigma, scale).
+    Within 1 float32 ulp of the fp64 SVD, with the start-vector exception stated in csrc/dip_sn.h."""
     import torch
     L = _lib.device_lib()
     n = len(weights)
