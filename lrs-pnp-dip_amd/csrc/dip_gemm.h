@@ -20,6 +20,7 @@
 
 #include "lrs_dip.h"
 #include "lrs_split.h"
+#include "dip_kernels.h"   // GemmArgs
 
 namespace lrs {
 
@@ -194,6 +195,18 @@ __device__ __forceinline__ void s3_store_pre(S3Tile &T, const RegP &r) {
     }
 }
 
+// load() of the four tap-table B loaders below (table tab [taps][128], K index tap * Cp + channel): the
+// step's tap and first channel, then the 16 channel planes (nc valid, pb bytes apart) of source S at the
+// thread's table entry.
+__device__ __forceinline__ void s3_tap_load(const float *S, int sbytes, const int *tab, int Cp, int nc, int pb, int k0,
+                                            int kend, float (&v)[16]) {
+    const int r0 = __builtin_amdgcn_readfirstlane(k0 + s3_kb<false>());
+    const int rr = r0 < kend ? r0 : 0,   // past the chunk: tap 0 (meets zero weights)
+              kyx = rr / Cp, c0 = rr - kyx * Cp;
+    const __amdgpu_buffer_rsrc_t rs = s3_rsrc(S, sbytes);
+    s3_bload_chans(rs, tab[kyx * 128 + s3_row<false>()], c0, nc, pb, v);
+}
+
 // Forward B: col[r][p] (k = r tap-major, x = output pixel p).  Table [kk][128] of the
 // workgroup's pixels' source byte offsets within a channel plane.
 struct LdFwdTM {
@@ -217,11 +230,7 @@ struct LdFwdTM {
         }
     }
     __device__ __forceinline__ void load(int, int k0, int kend, float (&v)[16]) const {
-        const int r0 = __builtin_amdgcn_readfirstlane(k0 + s3_kb<false>());
-        const int rr = r0 < kend ? r0 : 0,   // past the chunk: tap 0 (meets zero weights)
-                  kyx = rr / Cp, c0 = rr - kyx * Cp;
-        const __amdgpu_buffer_rsrc_t rs = s3_rsrc(X, xbytes);
-        s3_bload_chans(rs, tab[kyx * 128 + s3_row<false>()], c0, g.Cin, g.Hs * g.Ws * 4, v);
+        s3_tap_load(X, xbytes, tab, Cp, g.Cin, g.Hs * g.Ws * 4, k0, kend, v);
     }
 };
 
@@ -247,10 +256,7 @@ struct LdDgradTM {
         }
     }
     __device__ __forceinline__ void load(int, int k0, int kend, float (&v)[16]) const {
-        const int r0 = __builtin_amdgcn_readfirstlane(k0 + s3_kb<false>());
-        const int rr = r0 < kend ? r0 : 0, kyx = rr / Cop, c0 = rr - kyx * Cop;
-        const __amdgpu_buffer_rsrc_t rs = s3_rsrc(GY, gbytes);
-        s3_bload_chans(rs, tab[kyx * 128 + s3_row<false>()], c0, Cout, g.Ho * g.Wo * 4, v);
+        s3_tap_load(GY, gbytes, tab, Cop, Cout, g.Ho * g.Wo * 4, k0, kend, v);
     }
 };
 
@@ -349,10 +355,7 @@ struct LdUpFwdTM {
             tab[e * 128 + r] = in ? 4 * (clampi(a + (e >> 1) + i - 1, g.Hs) * g.Ws + clampi(b + (e & 1) + j - 1, g.Ws)) : kOob;
     }
     __device__ __forceinline__ void load(int, int k0, int kend, float (&v)[16]) const {
-        const int r0 = __builtin_amdgcn_readfirstlane(k0 + s3_kb<false>());
-        const int rr = r0 < kend ? r0 : 0, e = rr / Cp, c0 = rr - e * Cp;
-        const __amdgpu_buffer_rsrc_t rs = s3_rsrc(X, xbytes);
-        s3_bload_chans(rs, tab[e * 128 + s3_row<false>()], c0, g.Cin, g.Hs * g.Ws * 4, v);
+        s3_tap_load(X, xbytes, tab, Cp, g.Cin, g.Hs * g.Ws * 4, k0, kend, v);
     }
 };
 
@@ -380,10 +383,7 @@ struct LdUpDgradTM {
         }
     }
     __device__ __forceinline__ void load(int, int k0, int kend, float (&v)[16]) const {
-        const int r0 = __builtin_amdgcn_readfirstlane(k0 + s3_kb<false>());
-        const int rr = r0 < kend ? r0 : 0, ce = rr / Cop, c0 = rr - ce * Cop;
-        const __amdgpu_buffer_rsrc_t rs = s3_rsrc(GY, gbytes);
-        s3_bload_chans(rs, tab[ce * 128 + s3_row<false>()], c0, Cout, g.Ho * g.Wo * 4, v);
+        s3_tap_load(GY, gbytes, tab, Cop, Cout, g.Ho * g.Wo * 4, k0, kend, v);
     }
 };
 
@@ -727,563 +727,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_s3(GemmArgs g, LA la, LB lb) {
     __shared__ __attribute__((aligned(16))) S3Smem sm;
     gemm_s3_body(g, la, lb, sm, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), gridDim.x, gridDim.y,
                  gridDim.z);
-}
-
-// ---- pointwise (1x1, stride 1, unpadded) conv product -----------------------------------------
-// C[M][N] (+)= A[M][Kp] B[K][N] (+ bias[M]) for M <= 256 output channels over N pixels: the
-// forward (A = the k_wprep forward planes WF, B = x) and the data gradient (A = WD = W^T planes,
-// B = dL/dz) of the reference's 1x1 convs (my_Lipschitz_Unet.py:96-103, skip.py's 1x1 skips).
-// One workgroup per 64 pixels: their B columns (all K) are read from HBM once and split into the
-// three bf16 planes in LDS ([plane][pixel][k], row stride ldsrow bytes = 16 mod 256 so the 16
-// pixel rows of a fragment read sit in distinct bank groups); the pre-split A fragments stream
-// from L2 (one k-step prefetched), so every C element of the 64 pixels is produced by this one
-// workgroup: no split-K, no tile quantisation on M.  Wave w owns rows 16 w + 64 j (j < MT).
-struct PwArgs {
-    const __bf16 *A;
-    int64_t pstride;   // plane stride of A (elements)
-    int lda;           // A row length (Kp, multiple of 16; columns >= the valid K are zero)
-    const float *B;
-    int K;             // valid B rows
-    int64_t N;
-    float *C;
-    const float *bias;
-    int M, Kp32, ldsrow, accum;
-    int act;   // activation applied after the bias (a conv without BN: its act in the epilogue)
-    // the masked-MSE head fused into the network's last conv (tgt != NULL; k_mse_head's arithmetic per
-    // element): gz = act'(out) * (-norm (tgt m - out m) m) stored beside out, and per output row the
-    // workgroup's fp64 sums of gz and of (tgt m - out m)^2 in hpart[0 / 1][row][blockIdx.x].  The mask
-    // of output row m is read at m * mstride + n: mstride 0 for a [N] pixel mask, N for a per-element
-    // [M][N] one (read like tgt)
-    const float *tgt = nullptr, *msk = nullptr;
-    int64_t mstride = 0;
-    float *gz = nullptr;
-    double *hpart = nullptr;
-    float hnorm = 0.0f;
-};
-
-inline int pw_ldsrow(int Kp32) {   // bytes; Kp32 * 2 rounded up to 16 mod 256
-    int b = Kp32 * 2;
-    return b + (((16 - b) % 256) + 256) % 256;
-}
-
-// NB = 16-pixel column blocks per workgroup (16 NB pixels): 4, or 5, chosen per launch by
-// pw_launch (dipnet.hip) from the rounds of CU slots the grid needs.
-template <int MT, int NB = 4>
-__global__ __launch_bounds__(256, 2) void k_pw(PwArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char pw_smem[];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, jl = lane & 15, gk = lane >> 4;
-    constexpr int NPX = 16 * NB;
-    const int64_t n0 = (int64_t)blockIdx.x * NPX;
-    const int64_t plane = (int64_t)NPX * a.ldsrow;
-    if constexpr (NB == 4) {   // stage: thread (n = t & 63) splits k chunks (t >> 6) + 4 i of 8 values each.  Buffer
-        // loads, branch-free: k (wave-uniform) goes in the scalar offset, so rows k >= K fall past
-        // the buffer's K * N floats and read 0; a pixel n >= N reads at kOob.
-        const int n = t & 63;
-        const __amdgpu_buffer_rsrc_t rs = s3_rsrc(a.B, (int)(a.K * a.N * 4));
-        const int voff = n0 + n < a.N ? (int)((n0 + n) * 4) : kOob;
-        const int nck = a.Kp32 / 8, c0 = __builtin_amdgcn_readfirstlane(t >> 6);
-        float v[8][8];   // all of the thread's chunks (<= 8 for K <= 256) in flight together
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int c = c0 + 4 * i;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int64_t so = (int64_t)(8 * c + u) * a.N * 4;
-                v[i][u] = c < nck ? s3_bload(rs, voff, so < kOob ? (int)so : kOob) : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int c = c0 + 4 * i;
-            if (c >= nck) break;
-            bf16x8 p0, p1, p2;
-            split_bf16x8(v[i], p0, p1, p2);
-            char *dst = pw_smem + (int64_t)n * a.ldsrow + 16 * c;
-            *reinterpret_cast<bf16x8 *>(dst) = p0;
-            *reinterpret_cast<bf16x8 *>(dst + plane) = p1;
-            *reinterpret_cast<bf16x8 *>(dst + 2 * plane) = p2;
-        }
-    } else {   // NPX pixels x nck chunks as items it = t + 256 j: pixel it % NPX, chunk it / NPX
-        const __amdgpu_buffer_rsrc_t rs = s3_rsrc(a.B, (int)(a.K * a.N * 4));
-        const int nck = a.Kp32 / 8, items = NPX * nck;
-        constexpr int kMaxIt = (NPX * 32 + 255) / 256;   // K <= 256
-        float v[kMaxIt][8];
-#pragma unroll
-        for (int j = 0; j < kMaxIt; ++j) {
-            const int it = t + 256 * j, n = it % NPX, c = it / NPX;
-            const int voff = n0 + n < a.N ? (int)((n0 + n) * 4) : kOob;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int64_t so = (int64_t)(8 * c + u) * a.N * 4;
-                v[j][u] = it < items ? s3_bload(rs, voff, so < kOob ? (int)so : kOob) : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kMaxIt; ++j) {
-            const int it = t + 256 * j, n = it % NPX, c = it / NPX;
-            if (it >= items) break;
-            bf16x8 p0, p1, p2;
-            split_bf16x8(v[j], p0, p1, p2);
-            char *dst = pw_smem + (int64_t)n * a.ldsrow + 16 * c;
-            *reinterpret_cast<bf16x8 *>(dst) = p0;
-            *reinterpret_cast<bf16x8 *>(dst + plane) = p1;
-            *reinterpret_cast<bf16x8 *>(dst + 2 * plane) = p2;
-        }
-    }
-    floatx4 acc[MT][NB];
-#pragma unroll
-    for (int j = 0; j < MT; ++j)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[j][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-    const int ksteps = a.Kp32 / 32;
-    bf16x8 fa[MT][3], fn[MT][3];
-    // A fragments: 16-B buffer loads (L2-resident planes), rows >= M and k >= lda at kOob (zeros)
-    const __amdgpu_buffer_rsrc_t ra = s3_rsrc(a.A, (int)(3 * a.pstride * 2));
-    auto loadA = [&](int ks, bf16x8 (&f)[MT][3]) {
-        const int k = ks * 32 + 8 * gk;
-#pragma unroll
-        for (int j = 0; j < MT; ++j) {
-            const int row = 16 * wv + 64 * j + jl;
-            const int vo = (row < a.M && k < a.lda) ? 2 * (row * a.lda + k) : kOob;
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-                f[j][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, vo, (int)(2 * p * a.pstride), 0));
-        }
-    };
-    // NB = 4 prefetches the next k-step's A fragments; NB = 5 has no registers for that (its loads
-    // overlap the step's B fragment reads from LDS instead)
-    constexpr bool PF = NB == 4;
-    loadA(0, fa);
-    __syncthreads();
-    for (int ks = 0; ks < ksteps; ++ks) {
-        if constexpr (PF) {
-            if (ks + 1 < ksteps) loadA(ks + 1, fn);
-        } else if (ks > 0) {
-            loadA(ks, fa);
-        }
-        bf16x8 fb[NB][3];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const char *s0 = pw_smem + (int64_t)(16 * b + jl) * a.ldsrow + 16 * (4 * ks + gk);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fb[b][p] = *reinterpret_cast<const bf16x8 *>(s0 + p * plane);
-        }
-#pragma unroll
-        for (int j = 0; j < MT; ++j)
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[j][b] = split_mfma6(fa[j], fb[b], acc[j][b]);
-        if (PF && ks + 1 < ksteps) {
-#pragma unroll
-            for (int j = 0; j < MT; ++j)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) fa[j][p] = fn[j][p];
-        }
-    }
-    // epilogue through LDS (the B image is dead after this barrier): wave w writes its 16 x 64 tile
-    // of each row block as [row][pixel] and reads it back as float4 rows, so every 16 lanes store
-    // one full 256-B pixel run of a channel row (the MFMA layout gives a lane 4 rows of 1 pixel)
-    __syncthreads();
-    constexpr int ES = NPX + 4;   // staging row stride (floats)
-    float *E = reinterpret_cast<float *>(pw_smem) + wv * 16 * ES;
-    const bool vec = (a.N & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.C) & 15) == 0);
-    const bool head = a.tgt != nullptr;
-#pragma unroll
-    for (int j = 0; j < MT; ++j) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) E[(4 * gk + r) * ES + 16 * b + jl] = acc[j][b][r];
-        __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's LDS writes done (wave-local tile)
-        __builtin_amdgcn_wave_barrier();
-        double hs[NB], hb[NB];   // head: this lane's loss / bias-gradient sums of its run per i
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {   // 16 rows x NPX / 4 float4 runs
-            hs[i] = 0.0;
-            hb[i] = 0.0;
-            const int idx = lane + 64 * i, rr = idx / (4 * NB), q = 4 * (idx % (4 * NB));
-            const int m = 16 * wv + 64 * j + rr;
-            const int64_t n = n0 + q;
-            if (m >= a.M) continue;
-            float4 v = *reinterpret_cast<const float4 *>(E + rr * ES + q);
-            const float bs = a.bias ? a.bias[m] : 0.0f;
-            float *c = a.C + (int64_t)m * a.N + n;
-            if (vec && n + 3 < a.N) {
-                if (a.bias) { v.x = v.x + bs; v.y = v.y + bs; v.z = v.z + bs; v.w = v.w + bs; }
-                if (a.accum) {
-                    const float4 o = *reinterpret_cast<const float4 *>(c);
-                    v.x = o.x + v.x; v.y = o.y + v.y; v.z = o.z + v.z; v.w = o.w + v.w;
-                }
-                if (a.act) { v.x = act_fwd(v.x, a.act); v.y = act_fwd(v.y, a.act); v.z = act_fwd(v.z, a.act); v.w = act_fwd(v.w, a.act); }
-                *reinterpret_cast<float4 *>(c) = v;
-                if (head) {   // k_mse_head's per-element arithmetic, in the same order
-                    const float4 tv = *reinterpret_cast<const float4 *>(a.tgt + (int64_t)m * a.N + n);
-                    const float4 mv = a.msk ? *reinterpret_cast<const float4 *>(a.msk + (int64_t)m * a.mstride + n)
-                                            : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-                    const float oe[4] = {v.x, v.y, v.z, v.w}, te[4] = {tv.x, tv.y, tv.z, tv.w}, me[4] = {mv.x, mv.y, mv.z, mv.w};
-                    float ge[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float d = te[e] * me[e] - oe[e] * me[e];
-                        hs[i] += (double)d * (double)d;
-                        ge[e] = act_bwd((-(a.hnorm * d)) * me[e], oe[e], a.act);
-                        hb[i] += (double)ge[e];
-                    }
-                    *reinterpret_cast<float4 *>(a.gz + (int64_t)m * a.N + n) = make_float4(ge[0], ge[1], ge[2], ge[3]);
-                }
-            } else {
-                const float vv[4] = {v.x, v.y, v.z, v.w};
-                for (int u = 0; u < 4; ++u) {
-                    if (n + u >= a.N) break;
-                    float x = vv[u];
-                    if (a.bias) x = x + bs;
-                    if (a.accum) x = c[u] + x;
-                    if (a.act) x = act_fwd(x, a.act);
-                    c[u] = x;
-                    if (head) {
-                        const float mk = a.msk ? a.msk[(int64_t)m * a.mstride + n + u] : 1.0f;
-                        const float d = a.tgt[(int64_t)m * a.N + n + u] * mk - x * mk;
-                        hs[i] += (double)d * (double)d;
-                        const float g = act_bwd((-(a.hnorm * d)) * mk, x, a.act);
-                        a.gz[(int64_t)m * a.N + n + u] = g;
-                        hb[i] += (double)g;
-                    }
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (head) {   // each row's sums over the workgroup's runs, in run order, through this wave's LDS
-            double2 *R = reinterpret_cast<double2 *>(E);   // [16 rows x 4 NB runs] (fits the wave's E)
-            static_assert(16 * 4 * NB * sizeof(double2) <= 16 * ES * sizeof(float), "head sums fit the staging");
-#pragma unroll
-            for (int i = 0; i < NB; ++i) R[lane + 64 * i] = make_double2(hs[i], hb[i]);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-            const int m = 16 * wv + 64 * j + lane;
-            if (lane < 16 && m < a.M) {
-                double sl = 0.0, sg = 0.0;
-                for (int k = 0; k < 4 * NB; ++k) {
-                    const double2 p = R[lane * 4 * NB + k];
-                    sl += p.x;
-                    sg += p.y;
-                }
-                a.hpart[(int64_t)m * gridDim.x + blockIdx.x] = sg;
-                a.hpart[((int64_t)a.M + m) * gridDim.x + blockIdx.x] = sl;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-}
-
-// The fused head's sums (k_pw with PwArgs::tgt): per channel c (grid C) the gz sums of the nwg
-// workgroups, summed in a fixed order -> the conv's bias gradient, and the loss sums -> closs[c];
-// k_head_loss then adds closs in channel order into loss_acc (deterministic, as k_mse_head).
-__global__ __launch_bounds__(256) void k_head_reduce(const double *__restrict__ hpart, int C, int nwg, float *gbias,
-                                                     double *closs) {
-    __shared__ double red[12];
-    const int c = blockIdx.x;
-    double sg = 0.0, sl = 0.0;
-    for (int w = threadIdx.x; w < nwg; w += blockDim.x) {
-        sg += hpart[(int64_t)c * nwg + w];
-        sl += hpart[((int64_t)C + c) * nwg + w];
-    }
-    block_sum2_d(sg, sl, red);
-    if (threadIdx.x == 0) {
-        gbias[c] = (float)sg;
-        closs[c] = sl;
-    }
-}
-
-__global__ void k_head_loss(const double *__restrict__ closs, int C, double *loss_acc) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double s = 0.0;
-    for (int c = 0; c < C; ++c) s += closs[c];
-    *loss_acc += s;
-}
-
-// Per-step weight preparation of every conv of a network in ONE launch (grid (blocks, convs)):
-// Wn = W_bar / scale[si] for the spectrally normalised convs (lipschitz_constraint_layer.py:42-44)
-// and the bf16 planes the split-bf16 kernels read, from the same W / scale quotient:
-//   WF[p][co][kyx * Cp + ci]            forward operand (Cp = Cin rounded up to 16)
-//   WD[p][ci][kyx * Cop + co]           data-gradient operand (W^T, Cop = Cout rounded up to 16), or,
-//                                       for an upsampled stride-1 conv (ke > 0),
-//   WE[p][ci][(ey * ke + ex) * Cop + co] the effective ke x ke kernel of its data gradient as a
-//                                       stride-2 conv over dL/dz (conv_bwd): the sum of the taps
-//                                       W[a + k-1-ey][b + k-1-ex] over the 2 x 2 upsample children a, b
-//   upc: an upsampled reflection-padded 3 x 3 conv run by output parity class (LdUpFwdTM /
-//   LdUpDgradTM): instead of WF / WD,
-//   WUF[p][cls][co][e * Cp + ci]         the class's 2 x 2 effective weights (e = 2 ey + ex, the sum
-//                                        of W[co][ci][ky][kx] over ky in T(i, ey), kx in T(j, ex))
-//   WUD[p][ci][(4 cls + e) * Cop + co]   the same, transposed, all classes (the data gradient's K)
-struct ConvPrep {
-    const float *W;
-    float *Wn;          // nullable
-    __bf16 *wf, *wd;    // nullable (wd holds WE when ke > 0)
-    int Cout, Cin, kk, Cp, Cop, si, k, ke;   // si: scale index, -1 = no spectral norm
-    int upc;
-};
-
-// effective weight of parity class (i, j), tap (ey, ex): the taps T(i, ey) x T(j, ex) summed in
-// increasing ky, kx order (w = the 3 x 3 taps of one (co, ci))
-__device__ __forceinline__ float upc_weight(const float *w, int i, int j, int ey, int ex) {
-    const int y0 = (i == 0) ? (ey == 0 ? 0 : 1) : (ey == 0 ? 0 : 2), y1 = (i == 0) ? (ey == 0 ? 0 : 2) : (ey == 0 ? 1 : 2);
-    const int x0 = (j == 0) ? (ex == 0 ? 0 : 1) : (ex == 0 ? 0 : 2), x1 = (j == 0) ? (ex == 0 ? 0 : 2) : (ex == 0 ? 1 : 2);
-    float s = 0.0f;
-    for (int ky = y0; ky <= y1; ++ky)
-        for (int kx = x0; kx <= x1; ++kx) s = s + w[ky * 3 + kx];
-    return s;
-}
-
-__device__ __forceinline__ void conv_prep_body(const ConvPrep &c, float s, int64_t i0, int64_t stride) {
-    const int64_t nw = (int64_t)c.Cout * c.Cin * c.kk;
-    if (c.Wn)
-        for (int64_t i = i0; i < nw; i += stride) c.Wn[i] = c.W[i] / s;
-    const int ed = c.upc ? 16 : (c.ke > 0 ? c.ke * c.ke : c.kk);
-    // 32-bit index arithmetic (lrs_dipnet_create and the lrs_conv2d_* entry points reject a conv whose
-    // planes reach 2^31 / 3 elements)
-    const int nf = c.wf ? c.Cout * (c.upc ? 16 : c.kk) * c.Cp : 0, nd = c.wd ? c.Cin * ed * c.Cop : 0;
-    auto put = [&](__bf16 *dst, int plane, int j, float x) {
-        const Bf16Split q = split_bf16(x);
-        dst[j] = q.b0;
-        dst[plane + j] = q.b1;
-        dst[2 * plane + j] = q.b2;
-    };
-    // forward planes (ci fastest: the W reads of a wave are kk floats apart)
-    for (int i = (int)i0; i < nf; i += (int)stride) {
-        float x = 0.0f;
-        if (c.upc) {   // [cls][co][e * Cp + ci]
-            const int cl = i / (c.Cout * 4 * c.Cp), rem = i - cl * c.Cout * 4 * c.Cp;
-            const int co = rem / (4 * c.Cp), r = rem - co * 4 * c.Cp, e = r / c.Cp, ci = r - e * c.Cp;
-            if (ci < c.Cin) {
-                x = upc_weight(c.W + ((int64_t)co * c.Cin + ci) * 9, cl >> 1, cl & 1, e >> 1, e & 1);
-                if (c.si >= 0) x = x / s;
-            }
-        } else {       // [co][kyx * Cp + ci]
-            const int co = i / (c.kk * c.Cp), rem = i - co * c.kk * c.Cp, kyx = rem / c.Cp, ci = rem - kyx * c.Cp;
-            if (ci < c.Cin) {
-                x = c.W[((int64_t)co * c.Cin + ci) * c.kk + kyx];
-                if (c.si >= 0) x = x / s;
-            }
-        }
-        put(c.wf, nf, i, x);
-    }
-    // data-gradient planes [ci][e * Cop + co] (W^T): a wave covers 8 ci x 8 co of one e, so its W reads
-    // touch 8 rows of W instead of 64 (co fastest alone put the lanes Cin kk floats apart)
-    const int nci8 = (c.Cin + 7) / 8, ncob = c.Cop / 8, ndt = c.wd ? nci8 * 64 * ed * ncob : 0;
-    for (int t = (int)i0; t < ndt; t += (int)stride) {
-        const int l = t & 63, r = t >> 6;
-        const int cob = r % ncob, r2 = r / ncob, e = r2 % ed, cib = r2 / ed;
-        const int ci = 8 * cib + (l >> 3), co = 8 * cob + (l & 7);
-        if (ci >= c.Cin) continue;
-        float x = 0.0f;
-        if (co < c.Cout) {
-            const float *w = c.W + ((int64_t)co * c.Cin + ci) * c.kk;
-            if (c.upc) {   // e = 4 cls + tap
-                x = upc_weight(w, (e >> 2) >> 1, (e >> 2) & 1, (e & 3) >> 1, e & 1);
-            } else if (c.ke > 0) {
-                const int ey = e / c.ke, ex = e - ey * c.ke;
-                for (int a = 0; a < 2; ++a)
-                    for (int b = 0; b < 2; ++b) {
-                        const int ky = a + c.k - 1 - ey, kx = b + c.k - 1 - ex;
-                        if (ky >= 0 && ky < c.k && kx >= 0 && kx < c.k) x = x + w[ky * c.k + kx];
-                    }
-            } else {
-                x = w[e];
-            }
-            if (c.si >= 0) x = x / s;
-        }
-        put(c.wd, nd, (ci * ed + e) * c.Cop + co, x);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_conv_prep(const ConvPrep *__restrict__ tab, const float *__restrict__ scale,
-                                                   double *loss_acc, int *step) {
-    if (loss_acc && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {   // a training step begins
-        *loss_acc = 0.0;
-        *step += 1;
-    }
-    const ConvPrep c = tab[blockIdx.y];
-    conv_prep_body(c, c.si >= 0 ? scale[c.si] : 1.0f, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                   (int64_t)gridDim.x * blockDim.x);
-}
-
-// one conv, no spectral norm (the standalone lrs_conv2d_* entry points)
-__global__ __launch_bounds__(256) void k_conv_prep1(ConvPrep c) {
-    conv_prep_body(c, 1.0f, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
-}
-
-// Reflection-pad corrections of the effective-kernel data gradient of an upsampled, reflection-
-// padded 3 x 3 conv (pad 1).  The stride-2 4 x 4 conv over dL/dz treats the padded border as zeros;
-// the reference's ReflectionPad2d(1) also feeds padded row -1 from row 1 and row Hu from Hu - 2
-// (same for columns): extra (oy, ky) pairs (0, 0) -> source row 0 and (Hu - 1, 2) -> row Hs - 1,
-// and likewise (ox, kx) for the columns.  Four "lines": 0 / 1 = source rows 0 / Hs - 1 take every
-// term with a reflected row (any column, reflected or not); 2 / 3 = source columns 0 / Ws - 1 every
-// term with a reflected column and an unreflected row, so each term is counted once.  Three wide
-// launches (k_up_border_s, _mm, _add), scratch in the conv's col-gradient buffer:
-//   S[line][co][j][pos]  = the line's dL/dz summed over the positions that map to source pos via
-//                          tap j (j = kx for rows, ky for columns)
-//   corr[line][c][pos]   = sum_{co, j} W[co][c][tap(line, j)] S[line][co][j][pos]
-// then gx[c][perimeter pixel] += its row-line and column-line corrections.  w = the conv's fp32
-// weights (W / sigma) [Cout][Cin][3][3].
-constexpr int kUbC = 4, kUbCo = 32;
-
-__device__ __forceinline__ int ub_len(int line, int Hs, int Ws) { return line < 2 ? Ws : Hs; }
-
-__global__ __launch_bounds__(256) void k_up_border_s(const float *__restrict__ gz, int Cout, int Hs, int Ws, int Lmax,
-                                                     float *__restrict__ S) {
-    const int co = blockIdx.y, e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= 4 * 3 * Lmax) return;
-    const int line = e / (3 * Lmax), j = (e / Lmax) % 3, pos = e % Lmax;
-    const int Hu = 2 * Hs, Wu = 2 * Ws, rows = line < 2, L = ub_len(line, Hs, Ws), Lu = rows ? Wu : Hu;
-    float v = 0.0f;
-    if (pos < L) {
-        const int ofix = (line & 1) == 0 ? 0 : (rows ? Hu - 1 : Wu - 1);
-        const float *g = gz + (int64_t)co * Hu * Wu;
-        for (int o = max(0, 2 * pos - 2); o <= min(Lu - 1, 2 * pos + 3); ++o) {
-            int u = o + j - 1;
-            if (rows) u = u < 0 ? -u : (u >= Lu ? 2 * (Lu - 1) - u : u);   // along x: reflected ends included
-            else if (u < 0 || u >= Lu) continue;                          // along y: unreflected rows only
-            if ((u >> 1) == pos) v += g[rows ? (int64_t)ofix * Wu + o : (int64_t)o * Wu + ofix];
-        }
-    }
-    S[(((int64_t)line * Cout + co) * 3 + j) * Lmax + pos] = v;
-}
-
-__global__ __launch_bounds__(256) void k_up_border_mm(const float *__restrict__ S, const float *__restrict__ w, int Cin,
-                                                      int Cout, int Hs, int Ws, int Lmax, float *__restrict__ corr) {
-    __shared__ float Ss[kUbCo * 3 * 128], Wl[kUbCo * kUbC * 3];
-    const int line = blockIdx.x, c0 = blockIdx.y * kUbC, p0 = blockIdx.z * 128;
-    const int rows = line < 2, L = ub_len(line, Hs, Ws), tfix = (line & 1) == 0 ? 0 : 2;
-    const int cl = threadIdx.x >> 7, pl = threadIdx.x & 127;   // 2 channels x 128 positions per pass
-    float acc[2] = {0.0f, 0.0f};
-    for (int co0 = 0; co0 < Cout; co0 += kUbCo) {
-        __syncthreads();
-        float sv[kUbCo * 3 * 128 / 256];   // all 48 loads issued before any LDS store (clamped, then masked)
-#pragma unroll
-        for (int u = 0; u < kUbCo * 3 * 128 / 256; ++u) {
-            const int e = threadIdx.x + 256 * u;
-            const int col = e / 384, j = (e >> 7) % 3, pos = p0 + (e & 127), co = co0 + col;
-            const int cc = min(co, Cout - 1), pp = min(pos, Lmax - 1);
-            sv[u] = S[(((int64_t)line * Cout + cc) * 3 + j) * Lmax + pp];
-        }
-#pragma unroll
-        for (int u = 0; u < kUbCo * 3 * 128 / 256; ++u) {
-            const int e = threadIdx.x + 256 * u;
-            const int col = e / 384, pos = p0 + (e & 127), co = co0 + col;
-            Ss[e] = (co < Cout && pos < L) ? sv[u] : 0.0f;
-        }
-        for (int e = threadIdx.x; e < kUbCo * kUbC * 3; e += blockDim.x) {
-            const int col = e / (kUbC * 3), c = c0 + (e / 3) % kUbC, j = e % 3, co = co0 + col;
-            Wl[e] = (co < Cout && c < Cin) ? w[((int64_t)co * Cin + c) * 9 + (rows ? tfix * 3 + j : j * 3 + tfix)] : 0.0f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int c = 2 * h + cl;
-            float a = acc[h];
-            for (int col = 0; col < kUbCo; ++col)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) a = __fmaf_rn(Wl[(col * kUbC + c) * 3 + j], Ss[(col * 3 + j) * 128 + pl], a);
-            acc[h] = a;
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int c = c0 + 2 * h + cl, pos = p0 + pl;
-        if (c < Cin && pos < L) corr[((int64_t)line * Cin + c) * Lmax + pos] = acc[h];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_up_border_add(const float *__restrict__ corr, int Cin, int Hs, int Ws,
-                                                       int Lmax, float *__restrict__ gx) {
-    const int nper = 2 * Ws + 2 * (Hs - 2);
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
-    if (idx >= nper) return;
-    int sy, sx;
-    if (idx < Ws) { sy = 0; sx = idx; }
-    else if (idx < 2 * Ws) { sy = Hs - 1; sx = idx - Ws; }
-    else { const int r = idx - 2 * Ws; sy = 1 + (r >> 1); sx = (r & 1) ? Ws - 1 : 0; }
-    float v = 0.0f;
-    if (sy == 0) v += corr[((int64_t)0 * Cin + c) * Lmax + sx];
-    if (sy == Hs - 1) v += corr[((int64_t)1 * Cin + c) * Lmax + sx];
-    if (sx == 0) v += corr[((int64_t)2 * Cin + c) * Lmax + sy];
-    if (sx == Ws - 1) v += corr[((int64_t)3 * Cin + c) * Lmax + sy];
-    float *o = gx + ((int64_t)c * Hs + sy) * Ws + sx;
-    *o = *o + v;
-}
-
-// gx[c][sy][sx] (+)= sum over the x2 upsample children u of sum over the padded positions that
-// read u (direct + reflection mirrors, padded_sources) of gxp[c][iy][ix], where gxp is the sum of
-// nsplit split-K partials (stride zstride floats; the data-gradient GEMM's split-K finished here, in
-// k_gemm_reduce's order per position)
-__device__ __forceinline__ float fold_term(const float *__restrict__ src, int nsplit, int64_t zstride, int64_t i) {
-    if (nsplit == 1) return src[i];
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int z0 = 0; z0 < nsplit; z0 += 8) {
-        float p[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p[e] = z0 + e < nsplit ? src[(int64_t)(z0 + e) * zstride + i] : 0.0f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-            if (z0 + e < nsplit) acc[e] += p[e];
-    }
-    return ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-}
-
-__global__ __launch_bounds__(256) void k_fold_pad(const float *__restrict__ gxp, int nsplit, int64_t zstride,
-                                                  ConvGeom gm, float *__restrict__ gx, int accum) {
-    const int HW = gm.Hs * gm.Ws, Wp = gm.Wu + 2 * gm.pad, Qp = (gm.Hu + 2 * gm.pad) * Wp;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= HW) return;
-    const int sy = q / gm.Ws, sx = q - sy * gm.Ws;
-    const int nup = gm.up ? 2 : 1;
-    for (int c = blockIdx.y; c < gm.Cin; c += gridDim.y) {
-        const float *src = gxp + (int64_t)c * Qp;
-        float acc = 0.0f;
-        for (int a = 0; a < nup; ++a) {
-            int iys[3];
-            const int ny = padded_sources(gm.up ? 2 * sy + a : sy, gm.Hu, gm.pad, gm.pad_mode, iys);
-            for (int b = 0; b < nup; ++b) {
-                int ixs[3];
-                const int nx = padded_sources(gm.up ? 2 * sx + b : sx, gm.Wu, gm.pad, gm.pad_mode, ixs);
-                for (int py = 0; py < ny; ++py)
-                    for (int px = 0; px < nx; ++px) acc += fold_term(src, nsplit, zstride, iys[py] * Wp + ixs[px]);
-            }
-        }
-        const int64_t i = (int64_t)c * HW + q;
-        gx[i] = accum ? gx[i] + acc : acc;
-    }
-}
-
-// k_fold_pad for one partial (nsplit == 1, no upsample; a data-gradient GEMM with enough tiles, e.g.
-// the 512^2 layers of configs[3]): grid (row quads, Cin), a thread = 4 consecutive source x of one
-// row, float4 stores (Ws % 4 == 0).  Per pixel the same padded sources in the same order as
-// k_fold_pad, so the result is bit-identical.
-__global__ __launch_bounds__(256) void k_fold_pad1q(const float *__restrict__ gxp, ConvGeom gm, float *__restrict__ gx,
-                                                    int accum) {
-    const int W4 = gm.Ws >> 2, Wp = gm.Wu + 2 * gm.pad, Qp = (gm.Hu + 2 * gm.pad) * Wp;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= gm.Hs * W4) return;
-    const int c = blockIdx.y, sy = t / W4, sx0 = 4 * (t - sy * W4);
-    const float *src = gxp + (int64_t)c * Qp;
-    int iys[3];
-    const int ny = padded_sources(sy, gm.Hu, gm.pad, gm.pad_mode, iys);
-    float acc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        int ixs[3];
-        const int nx = padded_sources(sx0 + e, gm.Wu, gm.pad, gm.pad_mode, ixs);
-        float a = 0.0f;
-        for (int py = 0; py < ny; ++py)
-            for (int px = 0; px < nx; ++px) a += src[iys[py] * Wp + ixs[px]];
-        acc[e] = a;
-    }
-    float4 *o = reinterpret_cast<float4 *>(gx + ((int64_t)c * gm.Hs + sy) * gm.Ws + sx0);
-    float4 r = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    if (accum) {
-        const float4 p = *o;
-        r = make_float4(p.x + r.x, p.y + r.y, p.z + r.z, p.w + r.w);
-    }
-    *o = r;
 }
 
 }  // namespace lrs

@@ -4,7 +4,9 @@
 //   dip_bn.h     BatchNorm (+ Lipschitz rescale, + activation), every form, and which form serves a shape
 //   dip_sn.h     sigma_max of the conv weights (Gram, Lanczos + Sturm) and W / scale
 //   dip_train.h  loss heads, Adam, the step's begin, early stopping
-//   dip_gemm.h / dip_sm.h / dip_dir.h   the split-bf16, small-map and direct conv products
+//   dip_gemm.h / dip_pw.h / dip_sm.h / dip_dir.h   the split-bf16, pointwise, small-map and direct conv products
+//   dip_wprep.h  the per-step weight planes;  dip_dgrad.h  the kernels that finish a data gradient
+//   dip_image.h  image transforms, parameter initialisation
 //
 // Reference (shuoli0708/LRS-PnP-DIP):
 //   models/my_Lipschitz_Unet.py:21-148        the network (conv / bn / act stack)

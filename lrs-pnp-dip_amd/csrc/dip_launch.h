@@ -1,7 +1,7 @@
 // DIP low-rank prox, host side: conv geometry, tile and split-K choice, and the launchers of the
-// kernels in dip_kernels.h / dip_bn.h / dip_sn.h / dip_train.h / dip_gemm.h / dip_sm.h / dip_dir.h
-// (BatchNorm's form pickers and template dispatch are dip_bn.h's own).  Part of dipnet.hip's translation
-// unit (its only includer): the kernels defined here keep their internal linkage.
+// kernels in dip_kernels.h / dip_bn.h / dip_sn.h / dip_train.h / dip_gemm.h / dip_pw.h / dip_wprep.h /
+// dip_dgrad.h / dip_sm.h / dip_dir.h / dip_image.h (BatchNorm's form pickers and template dispatch are
+// dip_bn.h's own).  No kernel is defined here.  Part of dipnet.hip's translation unit.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -15,8 +15,12 @@
 #include "dip_sn.h"
 #include "dip_train.h"
 #include "dip_gemm.h"
+#include "dip_pw.h"
+#include "dip_wprep.h"
+#include "dip_dgrad.h"
 #include "dip_sm.h"
 #include "dip_dir.h"
+#include "dip_image.h"
 #include "ista_paths.h"
 
 using namespace lrs;
@@ -59,7 +63,15 @@ int make_geom(int Cin, int H, int W, int k, int stride, int pad, int pad_mode, i
     g.Ho = (hp - k) / stride + 1;
     g.Wo = (wp - k) / stride + 1;
     g.prec = o.precision;
-    // effective kernel of the upsampled data gradient as a stride-2 conv on the source grid
+    // Data gradient of an upsampled stride-1 conv (the U-Net's up_1..up_4: nearest x2, then 2 x 2 unpadded
+    // or reflection-padded 3 x 3) as a stride-2 conv over dL/dz with a (k+1) x (k+1) effective kernel on
+    // the source grid (dgrad_effective): 2.25x fewer products than correlating over the padded upsampled
+    // domain and folding.  ke = k + 1, or 0 where the identity is not used; fixed with the geometry: the
+    // workspace size, the weight-preparation table and the backward all read this one value.
+    // Off by default: measured in the whole 196^2 training step (bench configs[2], 2 x 2 A/B runs) it is
+    // ~1 % slower than the padded-domain correlation + fold -- the up_4 data-gradient work it saves ran
+    // beside that layer's weight gradient anyway, and it adds a split-K reduce and the border launches
+    // to the critical chain.  lrs_dip_opts::upsample_dgrad = 1 selects it (tests cover both).
     g.ke = 0;
     if (o.upsample_dgrad && g.up && g.stride == 1 && g.Hs >= 2 && g.Ws >= 2) {
         if (g.k == 3 && g.pad == 1) g.ke = 4;
@@ -128,6 +140,26 @@ inline void split_reduce(const Split &s, const float *part, int M, int N, const 
                            N, bias, div, accum, C);
 }
 
+// The tail every split-K product shares.  g holds the final output C; one split's partial is
+// [g.M][pcols] floats (pcols = g.N, or the whole row where the kernel scatters parity classes).  In order:
+// publish the split count; with more than one split (or to_part: a product whose own kernel sums its
+// partials) check the scratch and send the output there; launch(g, grid) over tiles x (zmul * S); sum
+// the partials into C (+ bias, / *div, accum) unless the caller finishes the sum (nsplit_out, to_part).
+template <class Launch>
+int split_launch(const Split &s, int64_t pcols, float *part, int64_t part_cap, GemmArgs g, dim3 tiles, int zmul,
+                 int *nsplit_out, hipStream_t st, Launch launch, bool to_part = false) {
+    if (nsplit_out) *nsplit_out = s.S;   // > 1: the caller finishes the split-K sum (no reduce here)
+    float *C = g.C;
+    if (s.S > 1 || to_part) {
+        if (!part || part_cap < (int64_t)s.S * g.M * pcols) return LRS_E_WORKSPACE;
+        g.C = part;
+    }
+    launch(g, dim3(tiles.x, tiles.y, (unsigned)(zmul * s.S)));
+    if (!nsplit_out && !to_part) split_reduce(s, part, g.M, (int)pcols, g.bias, g.div, g.accum, C, st);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
 // C = op(A) op(B) (+ bias) (/ *div); part: split-K scratch (>= gemm_part_floats); prec: the
 // conv's ConvGeom::prec
 int gemm(int prec, int TA, int TB, const float *A, const float *B, float *C, const float *bias, const float *div, int M,
@@ -135,46 +167,32 @@ int gemm(int prec, int TA, int TB, const float *A, const float *B, float *C, con
          bool force_big = false, int target = 512) {
     if (M <= 0 || N <= 0) return LRS_OK;
     const Split s = choose_split(M, N, K, prec, force_big, target);
-    if (nsplit_out) *nsplit_out = s.S;   // > 1: the caller finishes the split-K sum (no reduce here)
-    GemmArgs g{A, B, C, bias, div, M, N, K, s.kchunk, accum};
-    if (s.S > 1) {
-        if (!part || part_cap < (int64_t)s.S * M * N) return LRS_E_WORKSPACE;
-        g.C = part;
-    }
     const int t = (TA ? 2 : 0) + (TB ? 1 : 0);   // the f32 kernels by (TA, TB)
     static void (*const k128[4])(GemmArgs) = {k_gemm<0, 0>, k_gemm<0, 1>, k_gemm<1, 0>, k_gemm<1, 1>};
     static void (*const k64[4])(GemmArgs) = {k_gemm64<0, 0>, k_gemm64<0, 1>, k_gemm64<1, 0>, k_gemm64<1, 1>};
-    if (s.big && prec == LRS_DIP_SPLIT_BF16) {
-        dim3 grid((N + kBN - 1) / kBN, (M + kBM - 1) / kBM, s.S);
-        const int lda = TA ? M : K, ldb = TB ? K : N;
+    const dim3 tiles = s.big ? dim3((N + kBN - 1) / kBN, (M + kBM - 1) / kBM)
+                             : dim3((N + kBN64 - 1) / kBN64, (M + kBM64 - 1) / kBM64);
+    const auto launch = [&](const GemmArgs &g, dim3 grid) {
+        if (s.big && prec == LRS_DIP_SPLIT_BF16) {
+            const int lda = TA ? M : K, ldb = TB ? K : N;
 #define LRS_S3(RA, RB)                                                                                        \
     hipLaunchKernelGGL((k_gemm_s3<LdDense<RA>, LdDense<RB>>), grid, dim3(kGemmThreads), 0, st, g, LdDense<RA>{A, lda, M}, \
                        LdDense<RB>{B, ldb, N})
-        if (!TA && !TB) LRS_S3(true, false);
-        else if (!TA && TB) LRS_S3(true, true);
-        else if (TA && !TB) LRS_S3(false, false);
-        else LRS_S3(false, true);
+            if (!TA && !TB) LRS_S3(true, false);
+            else if (!TA && TB) LRS_S3(true, true);
+            else if (TA && !TB) LRS_S3(false, false);
+            else LRS_S3(false, true);
 #undef LRS_S3
-    } else if (s.big) {
-        hipLaunchKernelGGL(k128[t], dim3((N + kBN - 1) / kBN, (M + kBM - 1) / kBM, s.S), dim3(kGemmThreads), 0, st, g);
-    } else {
-        hipLaunchKernelGGL(k64[t], dim3((N + kBN64 - 1) / kBN64, (M + kBM64 - 1) / kBM64, s.S), dim3(kGemmThreads), 0, st, g);
-    }
-    if (!nsplit_out) split_reduce(s, part, M, N, bias, div, accum, C, st);
-    LRS_CHECK_LAUNCH();
-    return LRS_OK;
+        } else {
+            hipLaunchKernelGGL((s.big ? k128 : k64)[t], grid, dim3(kGemmThreads), 0, st, g);
+        }
+    };
+    return split_launch(s, N, part, part_cap, GemmArgs{A, B, C, bias, div, M, N, K, s.kchunk, accum}, tiles, 1, nsplit_out,
+                        st, launch);
 }
 
 inline int r16(int x) { return (x + 15) & ~15; }
 
-// Data gradient of an upsampled stride-1 conv (the U-Net's up_1..up_4: nearest x2, then 2 x 2 unpadded
-// or reflection-padded 3 x 3) as a stride-2 conv over dL/dz with a (k+1) x (k+1) effective kernel on
-// the source grid (conv_bwd): 2.25x fewer products than correlating over the padded upsampled domain
-// and folding.  Returns k + 1, or 0 where the identity is not used.
-// Off by default: measured in the whole 196^2 training step (bench configs[2], 2 x 2 A/B runs) it is
-// ~1 % slower than the padded-domain correlation + fold -- the up_4 data-gradient work it saves ran
-// beside that layer's weight gradient anyway, and it adds a split-K reduce and the border launches
-// to the critical chain.  lrs_dip_opts::upsample_dgrad = 1 selects it (tests cover both).
 // An upsampled, reflection-padded 3 x 3 stride-1 conv runs by output parity class in the network
 // engine (dip_gemm.h LdUpFwdTM / LdUpDgradTM, 4/9 of the direct products); every other upsampled conv
 // keeps the direct implicit GEMM over the upsampled grid.
@@ -182,8 +200,6 @@ inline bool upc_conv(const ConvGeom &g) {
     return g.up && g.k == 3 && g.pad == 1 && g.pad_mode == LRS_PAD_REFLECT && g.stride == 1 && g.Hs >= 2 && g.Ws >= 2;
 }
 
-// (ConvGeom::ke, fixed with the geometry: the workspace size, the weight-preparation table and the
-// backward all read this one value)
 // ---- small-map convs on k_conv_sm (dip_sm.h) ------------------------------------------------
 // A split-bf16 conv runs there when it is not 1x1, k <= 3 and its output map is below kImplicitMinP
 // (the maps that had the explicit im2col path).
@@ -214,16 +230,11 @@ int sm_launch(const LA &la, const LB &lb, float *C, const float *bias, int M, in
     if (M <= 0 || N <= 0) return LRS_OK;
     Split s = sm_split(M, N, K);
     if (one_launch) s = {1, (int)round_up(K, kSmK), false};
-    if (nsplit_out) *nsplit_out = s.S;
-    GemmArgs g{nullptr, nullptr, C, bias, div, M, N, K, s.kchunk, accum};
-    if (s.S > 1) {
-        if (!part || part_cap < (int64_t)s.S * M * N) return LRS_E_WORKSPACE;
-        g.C = part;
-    }
-    hipLaunchKernelGGL((k_conv_sm<LB, LA>), dim3((N + 63) / 64, (M + 63) / 64, s.S), dim3(256), 0, st, g, la, lb);
-    if (!nsplit_out) split_reduce(s, part, M, N, bias, div, accum, C, st);
-    LRS_CHECK_LAUNCH();
-    return LRS_OK;
+    const GemmArgs a{nullptr, nullptr, C, bias, div, M, N, K, s.kchunk, accum};
+    const auto launch = [&](const GemmArgs &g, dim3 grid) {
+        hipLaunchKernelGGL((k_conv_sm<LB, LA>), grid, dim3(256), 0, st, g, la, lb);
+    };
+    return split_launch(s, N, part, part_cap, a, dim3((N + 63) / 64, (M + 63) / 64), 1, nsplit_out, st, launch);
 }
 
 // The weight-gradient gather table of a small-map conv: for tap t and output pixel p, the byte
@@ -319,22 +330,18 @@ int64_t upc_part_floats(const ConvGeom &g, int Cout) {
     return std::max(m, (int64_t)w.S * 16 * Cout * g.Cin);
 }
 
-// bf16 elements of a conv's pre-split weight planes: forward operand WF [3][Cout][kk*Cp], then
-// the data-gradient operand WD [3][Cin][kk*Cop]
-// planes of the parity-class forward (WUF) / data gradient (WUD) when upc, else WF / WD (WE)
-inline int64_t wprep_fwd_elems(const ConvGeom &g, int Cout, bool upc = false) {
-    return 3 * (int64_t)Cout * (upc ? 16 : g.k * g.k) * r16(g.Cin);
-}
-inline int64_t wprep_elems(const ConvGeom &g, int Cout, bool upc) {
-    return wprep_fwd_elems(g, Cout, true) + 3 * (int64_t)g.Cin * 16 * r16(Cout);
-}
-inline int64_t wprep_elems(const ConvGeom &g, int Cout) {
-    const int ke = g.ke;
-    return wprep_fwd_elems(g, Cout) + 3 * (int64_t)g.Cin * (ke ? ke * ke : g.k * g.k) * r16(Cout);
+// bf16 elements of a conv's pre-split weight planes (dip_wprep.h): the forward operand's three planes
+// first -- WF [3][Cout][kk Cp], or by parity class (upc) WUF [3][4][Cout][4 Cp] -- then the data-gradient
+// operand's: WD [3][Cin][kk Cop], WE [3][Cin][ke^2 Cop] with an effective kernel, or WUD [3][Cin][16 Cop]
+struct WprepElems {
+    int64_t fwd, dgrad;
+    int64_t total() const { return fwd + dgrad; }
+};
+inline WprepElems wprep_elems(const ConvGeom &g, int Cout, bool upc) {
+    const int kk = g.k * g.k, taps_d = upc ? 16 : g.ke ? g.ke * g.ke : kk;
+    return {3 * (int64_t)Cout * (upc ? 16 : kk) * r16(g.Cin), 3 * (int64_t)g.Cin * taps_d * r16(Cout)};
 }
 
-// Implicit-GEMM conv product on the split-bf16 kernel, with the same split-K / reduce tail as
-// gemm().
 // split-K workgroup target of a forward conv whose partials a fused BN kernel finishes: fewer
 // splits than the GEMMs' 512 (the BN kernel, one workgroup per channel, re-reads every partial):
 // 196^2 step 1.336 -> 1.312 ms at 384 (A/B on one box: 256 1.317, 320 1.313).  The workspace is
@@ -346,23 +353,18 @@ constexpr int kFwdSplitWg = 384;
 // workspace is sized for.
 constexpr int kDgradSplitWg = 512;
 
+// Implicit-GEMM conv product on the split-bf16 kernel (always 128-tiles), with gemm()'s split-K tail.
 template <class LA, class LB>
 int gemm_s3_conv(const LA &la, const LB &lb, float *C, const float *bias, const float *div, int M, int N, int K,
                  float *part, int64_t part_cap, hipStream_t st, int *nsplit_out = nullptr, int accum = 0,
                  int target = 512) {
     if (M <= 0 || N <= 0) return LRS_OK;
     const Split s = choose_split(M, N, K, LRS_DIP_SPLIT_BF16, true, target);
-    if (nsplit_out) *nsplit_out = s.S;
-    GemmArgs g{nullptr, nullptr, C, bias, div, M, N, K, s.kchunk, accum};
-    if (s.S > 1) {
-        if (!part || part_cap < (int64_t)s.S * M * N) return LRS_E_WORKSPACE;
-        g.C = part;
-    }
-    dim3 grid((N + 127) / 128, (M + 127) / 128, s.S);
-    hipLaunchKernelGGL((k_gemm_s3<LA, LB>), grid, dim3(kGemmThreads), 0, st, g, la, lb);
-    if (!nsplit_out) split_reduce(s, part, M, N, bias, div, accum, C, st);
-    LRS_CHECK_LAUNCH();
-    return LRS_OK;
+    const GemmArgs a{nullptr, nullptr, C, bias, div, M, N, K, s.kchunk, accum};
+    const auto launch = [&](const GemmArgs &g, dim3 grid) {
+        hipLaunchKernelGGL((k_gemm_s3<LA, LB>), grid, dim3(kGemmThreads), 0, st, g, la, lb);
+    };
+    return split_launch(s, N, part, part_cap, a, dim3((N + 127) / 128, (M + 127) / 128), 1, nsplit_out, st, launch);
 }
 
 // Forward of an upsampled 3 x 3 conv by output parity class: one launch, gridDim.z = 4 classes x
@@ -372,19 +374,13 @@ int upc_fwd(const ConvGeom &g, const float *x, const __bf16 *wpre, const float *
     const int Cp = r16(g.Cin), Q = g.Hs * g.Ws, K = 4 * Cp;
     const int64_t P = (int64_t)g.Ho * g.Wo;
     const Split s = choose_split(Cout, 4 * Q, K, LRS_DIP_SPLIT_BF16, true, nsplit_out ? kFwdSplitWg : 512);
-    if (nsplit_out) *nsplit_out = s.S;
-    GemmArgs a{nullptr, nullptr, y, bias, nullptr, Cout, Q, K, s.kchunk, 0, 4, g.Ws, g.Wo, P};
-    if (s.S > 1) {
-        if (!part || part_cap < (int64_t)s.S * Cout * P) return LRS_E_WORKSPACE;
-        a.C = part;
-    }
-    const dim3 grid((Q + 127) / 128, (Cout + 127) / 128, 4 * s.S);
-    hipLaunchKernelGGL((k_gemm_s3<LdPre, LdUpFwdTM>), grid, dim3(kGemmThreads), 0, st, a,
-                       LdPre{wpre, (int64_t)4 * Cout * K, K, Cout, (int64_t)Cout * K},
-                       LdUpFwdTM{x, g.Cin * Q * 4, g, Cp, nullptr});
-    if (!nsplit_out) split_reduce(s, part, Cout, (int)P, bias, nullptr, 0, y, st);
-    LRS_CHECK_LAUNCH();
-    return LRS_OK;
+    const GemmArgs a{nullptr, nullptr, y, bias, nullptr, Cout, Q, K, s.kchunk, 0, 4, g.Ws, g.Wo, P};
+    const auto launch = [&](const GemmArgs &ga, dim3 grid) {
+        hipLaunchKernelGGL((k_gemm_s3<LdPre, LdUpFwdTM>), grid, dim3(kGemmThreads), 0, st, ga,
+                           LdPre{wpre, (int64_t)4 * Cout * K, K, Cout, (int64_t)Cout * K},
+                           LdUpFwdTM{x, g.Cin * Q * 4, g, Cp, nullptr});
+    };
+    return split_launch(s, P, part, part_cap, a, dim3((Q + 127) / 128, (Cout + 127) / 128), 4, nsplit_out, st, launch);
 }
 
 // Its data gradient: gxe over the source grid extended by one pixel (one GEMM with K = 4 classes x
@@ -418,11 +414,15 @@ int upc_wgrad(const ConvGeom &g, const float *gz, const float *x, const float *d
               int64_t part_cap, hipStream_t st, int target = 512) {
     const int Q = g.Hs * g.Ws, N = 4 * g.Cin;
     const Split s = choose_split(Cout, 4 * N, Q, LRS_DIP_SPLIT_BF16, true, target);
-    if (!part || part_cap < (int64_t)s.S * 4 * Cout * N) return LRS_E_WORKSPACE;
     const GemmArgs a{nullptr, nullptr, part, nullptr, nullptr, Cout, N, Q, s.kchunk, 0, 4, g.Ws, 0, 0};
-    const dim3 grid((N + 127) / 128, (Cout + 127) / 128, 4 * s.S);
-    hipLaunchKernelGGL((k_gemm_s3<LdGzCls, LdWgradCls>), grid, dim3(kGemmThreads), 0, st, a,
-                       LdGzCls{gz, g.Hs, g.Ws, g.Wo, Cout, 0}, LdWgradCls{x, g.Cin * Q * 4, g, nullptr, 0, 0});
+    const auto launch = [&](const GemmArgs &ga, dim3 grid) {
+        hipLaunchKernelGGL((k_gemm_s3<LdGzCls, LdWgradCls>), grid, dim3(kGemmThreads), 0, st, ga,
+                           LdGzCls{gz, g.Hs, g.Ws, g.Wo, Cout, 0}, LdWgradCls{x, g.Cin * Q * 4, g, nullptr, 0, 0});
+    };
+    // to_part: the partials go to the scratch with one split too (k_upc_wgrad_combine sums the classes)
+    const int rc = split_launch(s, 4 * N, part, part_cap, a, dim3((N + 127) / 128, (Cout + 127) / 128), 4, nullptr, st, launch,
+                                true);
+    if (rc) return rc;
     const int64_t n = (int64_t)Cout * g.Cin * 9;
     hipLaunchKernelGGL(k_upc_wgrad_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, s.S, Cout, g.Cin,
                        div, gw);
@@ -446,8 +446,9 @@ constexpr int64_t kImplicitMinP = 1024;
 // split w into the bf16 planes of the forward operand (and of the data-gradient one if wd)
 int wprep(const ConvGeom &g, const float *w, int Cout, __bf16 *wf, __bf16 *wd, hipStream_t st) {
     const int kk = g.k * g.k;
-    if (wprep_elems(g, Cout) >= INT32_MAX / 3) return LRS_E_UNSUPPORTED;   // k_conv_prep's 32-bit indices
-    const int64_t n = wprep_elems(g, Cout) / 3;
+    const int64_t elems = wprep_elems(g, Cout, false).total();
+    if (elems >= INT32_MAX / 3) return LRS_E_UNSUPPORTED;   // k_conv_prep's 32-bit indices
+    const int64_t n = elems / 3;
     const ConvPrep c{w, nullptr, wf, wd, Cout, g.Cin, kk, r16(g.Cin), r16(Cout), -1, g.k, wd ? g.ke : 0};
     hipLaunchKernelGGL(k_conv_prep1, dim3(ew_blocks(n, 2048)), dim3(256), 0, st, c);
     return LRS_OK;
@@ -551,99 +552,120 @@ int conv_fwd(const ConvGeom &g, const float *x, const float *w, const float *bia
     return gemm(g.prec, 0, 0, w, B, y, bias, nullptr, Cout, P, Kc, part, part_cap, st, 0, nsplit_out);
 }
 
-// gw = gz col^T / div ; gx = col2im(w^T gz) (gw, gx nullable).  dcol: Kc*P floats when !plain.
-// implicit: `col` is the conv input x, col^T is gathered inside the GEMM, and wpre holds the
-// weight planes (wprep) for the stride-1 data gradient.
-int conv_bwd(const ConvGeom &g, const float *gz, const float *col, const float *w, const float *div, int Cout,
-             float *gx, float *gw, float *dcol, float *part, int64_t part_cap, hipStream_t st, int accum_gx = 0,
-             bool implicit = false, const __bf16 *wpre = nullptr, int *wsplit_out = nullptr, int wtarget = 512) {
-    const int P = g.Ho * g.Wo, kk = g.k * g.k, Kc = g.Cin * kk;
-    int rc;
-    implicit = implicit && !plain_unit(g);
-    rc = LRS_OK;
-    if (!gw) {
-        // data gradient only (the weight gradient runs elsewhere)
-    } else if (implicit) {
+// gw = gz col^T / *div.  implicit (a conv that is not 1x1): `col` is the conv input x and col^T is gathered
+// inside the GEMM.  wsplit_out: the caller finishes the split-K sum (k_adam's AdamPend).
+int conv_wgrad(const ConvGeom &g, const float *gz, const float *col, const float *div, int Cout, float *gw, float *part,
+               int64_t part_cap, hipStream_t st, bool implicit, int *wsplit_out = nullptr, int wtarget = 512) {
+    const int P = g.Ho * g.Wo, Kc = g.Cin * g.k * g.k;
+    if (implicit && !plain_unit(g)) {
         if (!conv_implicit_ok(g, Cout)) return LRS_E_UNSUPPORTED;
-        // wsplit_out: the caller finishes the split-K sum (k_adam's AdamPend)
-        rc = gemm_s3_conv(LdDense<true>{gz, P, Cout}, LdWgradTM{col, g.Cin * g.Hs * g.Ws * 4, g, nullptr, 0}, gw,
-                          nullptr, div, Cout, Kc, P, part, part_cap, st, wsplit_out, 0, wtarget);
-    } else {
-        // a 1x1 conv's weight gradient (K = all pixels): 128-tiles with deep split-K on the split-bf16
-        // kernel (A/B in the 196^2 training step, configs[2]: 5.50 -> 5.65 outer it/s against the f32
-        // 64-tile kernel; alone the two are within 12 %, but the f32 kernel's 512 workgroups hold the
-        // CUs the concurrent data-gradient chain needs for longer)
-        // (wsplit_out: as above, the caller's k_adam finishes the split-K sum)
-        rc = gemm(g.prec, 0, 1, gz, col, gw, nullptr, div, Cout, Kc, P, part, part_cap, st, 0, wsplit_out, plain_unit(g),
-                  wtarget);
+        return gemm_s3_conv(LdDense<true>{gz, P, Cout}, LdWgradTM{col, g.Cin * g.Hs * g.Ws * 4, g, nullptr, 0}, gw,
+                            nullptr, div, Cout, Kc, P, part, part_cap, st, wsplit_out, 0, wtarget);
     }
-    if (rc || !gx) return rc;
-    if (plain_unit(g) && wpre)      // 1x1 data gradient: W^T planes (wprep's WD)
-        return pw_launch(wpre + wprep_fwd_elems(g, Cout), (int64_t)g.Cin * r16(Cout), r16(Cout), g.Cin, gz, Cout, P,
-                         gx, nullptr, accum_gx, st);
-    if (plain_unit(g)) return gemm(g.prec, 1, 0, w, gz, gx, nullptr, nullptr, Kc, P, Cout, part, part_cap, st, accum_gx);
-    const int ke = g.ke;
-    const bool refl_border = g.pad_mode == LRS_PAD_REFLECT && g.k == 3;
-    const int Lmax = std::max(g.Ws, g.Hs);
-    // the border scratch (S and corr) lives in the col-gradient buffer, unused on this path
-    const bool border_fits = dcol && (int64_t)4 * (3 * Cout + g.Cin) * Lmax <= (int64_t)g.Cin * g.k * g.k * P;
-    if (implicit && wpre && ke && !accum_gx && (!refl_border || border_fits)) {
-        // gx = the stride-2 (ke x ke, zero pad 1) conv of dL/dz with the effective weights WE
-        // (k_conv_prep), then the reflection terms of the border rows / columns
-        const int Cop = r16(Cout), ke2 = ke * ke;
-        ConvGeom ge{};
-        ge.Cin = Cout; ge.Hs = g.Ho; ge.Ws = g.Wo; ge.up = 0; ge.Hu = g.Ho; ge.Wu = g.Wo;
-        ge.pad = 1; ge.pad_mode = LRS_PAD_ZERO; ge.k = ke; ge.stride = 2; ge.Ho = g.Hs; ge.Wo = g.Ws;
-        if ((g.Ho + 2 - ke) / 2 + 1 != g.Hs || (g.Wo + 2 - ke) / 2 + 1 != g.Ws) return LRS_E_INVALID;
-        rc = gemm_s3_conv(LdPre{wpre + wprep_fwd_elems(g, Cout), (int64_t)g.Cin * ke2 * Cop, ke2 * Cop, g.Cin},
-                          LdFwdTM{gz, Cout * P * 4, ge, Cop, nullptr}, gx, nullptr, nullptr, g.Cin, g.Hs * g.Ws,
-                          ke2 * Cop, part, part_cap, st);
-        if (rc) return rc;
-        if (refl_border) {
-            float *S = dcol, *corr = dcol + (int64_t)4 * 3 * Cout * Lmax;
-            hipLaunchKernelGGL(k_up_border_s, dim3((unsigned)((12 * Lmax + 255) / 256), (unsigned)Cout), dim3(256), 0, st,
-                               gz, Cout, g.Hs, g.Ws, Lmax, S);
-            hipLaunchKernelGGL(k_up_border_mm, dim3(4, (unsigned)((g.Cin + kUbC - 1) / kUbC), (unsigned)((Lmax + 127) / 128)),
-                               dim3(256), 0, st, S, w, g.Cin, Cout, g.Hs, g.Ws, Lmax, corr);
-            const int nper = 2 * g.Ws + 2 * (g.Hs - 2);
-            hipLaunchKernelGGL(k_up_border_add, dim3((unsigned)((nper + 255) / 256), (unsigned)g.Cin), dim3(256), 0, st,
-                               corr, g.Cin, g.Hs, g.Ws, Lmax, gx);
-        }
-        LRS_CHECK_LAUNCH();
-        return LRS_OK;
-    }
-    if (!dcol) return LRS_E_WORKSPACE;
-    const int Qp = (g.Hu + 2 * g.pad) * (g.Wu + 2 * g.pad);
-    if (implicit && wpre && g.stride == 1 && (int64_t)g.Cin * Qp <= (int64_t)Kc * P) {
-        // gxp = W^T (x) gz over the padded domain (implicit, in the dcol space), then fold the
-        // padding / upsample
-        const int Cop = r16(Cout);
-        const __bf16 *wd = wpre + wprep_fwd_elems(g, Cout);
-        int nsplit = 1;   // split-K partials are summed inside the fold
-        rc = gemm_s3_conv(LdPre{wd, (int64_t)g.Cin * kk * Cop, kk * Cop, g.Cin},
-                          LdDgradTM{gz, Cout * P * 4, g, Cout, Cop, nullptr}, dcol, nullptr, nullptr, g.Cin, Qp,
-                          kk * Cop, part, part_cap, st, &nsplit, 0, kDgradSplitWg);
-        if (rc) return rc;
-        if (nsplit == 1 && !g.up && g.Ws % 4 == 0 && g.Cin <= 65535 && ((uintptr_t)gx & 15) == 0) {   // one partial: row quads
-            const int q = g.Hs * (g.Ws / 4);
-            hipLaunchKernelGGL(k_fold_pad1q, dim3((unsigned)((q + 255) / 256), (unsigned)g.Cin), dim3(256), 0, st, dcol,
-                               g, gx, accum_gx);
-        } else {
-            const dim3 grid((unsigned)((g.Hs * g.Ws + 255) / 256), (unsigned)std::min(g.Cin, 65535));
-            hipLaunchKernelGGL(k_fold_pad, grid, dim3(256), 0, st, nsplit > 1 ? part : dcol, nsplit, (int64_t)g.Cin * Qp,
-                               g, gx, accum_gx);
-        }
-        LRS_CHECK_LAUNCH();
-        return LRS_OK;
-    }
-    rc = gemm(g.prec, 1, 0, w, gz, dcol, nullptr, nullptr, Kc, P, Cout, part, part_cap, st);
+    // a 1x1 conv's weight gradient (K = all pixels): 128-tiles with deep split-K on the split-bf16
+    // kernel (A/B in the 196^2 training step, configs[2]: 5.50 -> 5.65 outer it/s against the f32
+    // 64-tile kernel; alone the two are within 12 %, but the f32 kernel's 512 workgroups hold the
+    // CUs the concurrent data-gradient chain needs for longer)
+    return gemm(g.prec, 0, 1, gz, col, gw, nullptr, div, Cout, Kc, P, part, part_cap, st, 0, wsplit_out, plain_unit(g),
+                wtarget);
+}
+
+// ---- the four forms of a conv's data gradient gx (+)= conv^T(dL/dz); conv_dgrad picks one ----------
+
+// 1x1: k_pw on the W^T planes (wprep's WD) where the conv has planes, else the dense GEMM W^T gz
+int dgrad_pointwise(const ConvGeom &g, const float *gz, const float *w, const __bf16 *wpre, int Cout, float *gx,
+                    float *part, int64_t part_cap, hipStream_t st, int accum) {
+    const int P = g.Ho * g.Wo;
+    if (wpre)
+        return pw_launch(wpre + wprep_elems(g, Cout, false).fwd, (int64_t)g.Cin * r16(Cout), r16(Cout), g.Cin, gz, Cout, P,
+                         gx, nullptr, accum, st);
+    return gemm(g.prec, 1, 0, w, gz, gx, nullptr, nullptr, g.Cin, P, Cout, part, part_cap, st, accum);
+}
+
+// An upsampled stride-1 conv with an effective kernel (ConvGeom::ke): gx = the stride-2 (ke x ke, zero
+// pad 1) conv of dL/dz with the effective weights we (k_conv_prep's WE), then the reflection terms of
+// the border rows / columns (dip_dgrad.h k_up_border_*; border: their scratch S and corr)
+int dgrad_effective(const ConvGeom &g, const float *gz, const float *w, const __bf16 *we, int Cout, float *gx,
+                    float *border, float *part, int64_t part_cap, hipStream_t st) {
+    const int P = g.Ho * g.Wo, ke = g.ke, Cop = r16(Cout), ke2 = ke * ke;
+    ConvGeom ge{};
+    ge.Cin = Cout; ge.Hs = g.Ho; ge.Ws = g.Wo; ge.up = 0; ge.Hu = g.Ho; ge.Wu = g.Wo;
+    ge.pad = 1; ge.pad_mode = LRS_PAD_ZERO; ge.k = ke; ge.stride = 2; ge.Ho = g.Hs; ge.Wo = g.Ws;
+    if ((g.Ho + 2 - ke) / 2 + 1 != g.Hs || (g.Wo + 2 - ke) / 2 + 1 != g.Ws) return LRS_E_INVALID;
+    const int rc = gemm_s3_conv(LdPre{we, (int64_t)g.Cin * ke2 * Cop, ke2 * Cop, g.Cin},
+                                LdFwdTM{gz, Cout * P * 4, ge, Cop, nullptr}, gx, nullptr, nullptr, g.Cin, g.Hs * g.Ws,
+                                ke2 * Cop, part, part_cap, st);
     if (rc) return rc;
-    const dim3 grid((unsigned)((g.Hs * g.Ws + 255) / 256), (unsigned)std::min(g.Cin, 65535));
-    if (g.stride == 1) hipLaunchKernelGGL(k_col2im<1>, grid, dim3(256), 0, st, dcol, g, gx, accum_gx);
-    else if (g.stride == 2) hipLaunchKernelGGL(k_col2im<2>, grid, dim3(256), 0, st, dcol, g, gx, accum_gx);
-    else hipLaunchKernelGGL(k_col2im<0>, grid, dim3(256), 0, st, dcol, g, gx, accum_gx);
+    if (g.pad_mode == LRS_PAD_REFLECT && g.k == 3) {
+        const int Lmax = std::max(g.Ws, g.Hs);
+        float *S = border, *corr = border + (int64_t)4 * 3 * Cout * Lmax;
+        hipLaunchKernelGGL(k_up_border_s, dim3((unsigned)((12 * Lmax + 255) / 256), (unsigned)Cout), dim3(256), 0, st,
+                           gz, Cout, g.Hs, g.Ws, Lmax, S);
+        hipLaunchKernelGGL(k_up_border_mm, dim3(4, (unsigned)((g.Cin + kUbC - 1) / kUbC), (unsigned)((Lmax + 127) / 128)),
+                           dim3(256), 0, st, S, w, g.Cin, Cout, g.Hs, g.Ws, Lmax, corr);
+        const int nper = 2 * g.Ws + 2 * (g.Hs - 2);
+        hipLaunchKernelGGL(k_up_border_add, dim3((unsigned)((nper + 255) / 256), (unsigned)g.Cin), dim3(256), 0, st,
+                           corr, g.Cin, g.Hs, g.Ws, Lmax, gx);
+    }
     LRS_CHECK_LAUNCH();
     return LRS_OK;
+}
+
+// Stride 1: gxp = W^T (x) gz over the padded, upsampled domain (implicit GEMM on the WD planes wd, into
+// dcol), then the fold of the padding / upsample, which also sums the split-K partials
+int dgrad_padded(const ConvGeom &g, const float *gz, const __bf16 *wd, int Cout, float *gx, float *dcol, float *part,
+                 int64_t part_cap, hipStream_t st, int accum) {
+    const int P = g.Ho * g.Wo, kk = g.k * g.k, Cop = r16(Cout), Qp = (g.Hu + 2 * g.pad) * (g.Wu + 2 * g.pad);
+    int nsplit = 1;
+    const int rc = gemm_s3_conv(LdPre{wd, (int64_t)g.Cin * kk * Cop, kk * Cop, g.Cin},
+                                LdDgradTM{gz, Cout * P * 4, g, Cout, Cop, nullptr}, dcol, nullptr, nullptr, g.Cin, Qp,
+                                kk * Cop, part, part_cap, st, &nsplit, 0, kDgradSplitWg);
+    if (rc) return rc;
+    if (nsplit == 1 && !g.up && g.Ws % 4 == 0 && g.Cin <= 65535 && ((uintptr_t)gx & 15) == 0) {   // one partial: row quads
+        const int q = g.Hs * (g.Ws / 4);
+        hipLaunchKernelGGL(k_fold_pad1q, dim3((unsigned)((q + 255) / 256), (unsigned)g.Cin), dim3(256), 0, st, dcol,
+                           g, gx, accum);
+    } else {
+        const dim3 grid((unsigned)((g.Hs * g.Ws + 255) / 256), (unsigned)std::min(g.Cin, 65535));
+        hipLaunchKernelGGL(k_fold_pad, grid, dim3(256), 0, st, nsplit > 1 ? part : dcol, nsplit, (int64_t)g.Cin * Qp,
+                           g, gx, accum);
+    }
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
+// Any geometry: dcol = W^T gz (explicit, Kc x P floats), then col2im
+int dgrad_col2im(const ConvGeom &g, const float *gz, const float *w, int Cout, float *gx, float *dcol, float *part,
+                 int64_t part_cap, hipStream_t st, int accum) {
+    const int P = g.Ho * g.Wo, Kc = g.Cin * g.k * g.k;
+    const int rc = gemm(g.prec, 1, 0, w, gz, dcol, nullptr, nullptr, Kc, P, Cout, part, part_cap, st);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((g.Hs * g.Ws + 255) / 256), (unsigned)std::min(g.Cin, 65535));
+    if (g.stride == 1) hipLaunchKernelGGL(k_col2im<1>, grid, dim3(256), 0, st, dcol, g, gx, accum);
+    else if (g.stride == 2) hipLaunchKernelGGL(k_col2im<2>, grid, dim3(256), 0, st, dcol, g, gx, accum);
+    else hipLaunchKernelGGL(k_col2im<0>, grid, dim3(256), 0, st, dcol, g, gx, accum);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
+// gx (+)= col2im(w^T gz).  dcol: Kc * P floats when the conv is not 1x1 (NULL: only the forms without it).
+// implicit with wpre (the weight planes from wprep / k_conv_prep): the data gradient reads the planes
+// after the forward operand's (WD, or WE with an effective kernel).
+int conv_dgrad(const ConvGeom &g, const float *gz, const float *w, int Cout, float *gx, float *dcol, float *part,
+               int64_t part_cap, hipStream_t st, int accum, bool implicit, const __bf16 *wpre) {
+    if (plain_unit(g)) return dgrad_pointwise(g, gz, w, wpre, Cout, gx, part, part_cap, st, accum);
+    const __bf16 *wd = (implicit && wpre) ? wpre + wprep_elems(g, Cout, false).fwd : nullptr;
+    const int P = g.Ho * g.Wo, Kc = g.Cin * g.k * g.k;
+    const bool refl_border = g.pad_mode == LRS_PAD_REFLECT && g.k == 3;
+    // the border scratch (S and corr) lives in the col-gradient buffer, unused on that path
+    const bool border_fits = dcol && (int64_t)4 * (3 * Cout + g.Cin) * std::max(g.Ws, g.Hs) <= (int64_t)Kc * P;
+    if (wd && g.ke && !accum && (!refl_border || border_fits))
+        return dgrad_effective(g, gz, w, wd, Cout, gx, dcol, part, part_cap, st);
+    if (!dcol) return LRS_E_WORKSPACE;
+    const int Qp = (g.Hu + 2 * g.pad) * (g.Wu + 2 * g.pad);
+    if (wd && g.stride == 1 && (int64_t)g.Cin * Qp <= (int64_t)Kc * P)
+        return dgrad_padded(g, gz, wd, Cout, gx, dcol, part, part_cap, st, accum);
+    return dgrad_col2im(g, gz, w, Cout, gx, dcol, part, part_cap, st, accum);
 }
 
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -708,37 +730,6 @@ void dir_launch(const ConvGeom &g, const DirGeom &dg, const float *x, const floa
 #undef LRS_DIR
 }
 
-// The step head of the overlapped sigma (lrs_dipnet::sn_overlap): the spectral-norm Gram partials of
-// the n convs (blockIdx.y < n, k_sn_gram's body) and, in the extra row blockIdx.y == n, the first
-// conv's forward planes from the raw weights (the head ConvPrep) with the step's loss reset and Adam
-// step count: one launch instead of two.
-// kHeadPlaneRows: the first conv's planes on 8 grid rows of kSnSplit workgroups (one row: the kernel took
-// 36.7 us, its 16 plane workgroups the longest; 8 rows: 19.2 us, 196^2 step 1.194 -> 1.177 ms, 3 interleaved
-// rounds, profiles/r06/ab/head_plane_rows.txt)
-constexpr int kHeadPlaneRows = 8;
-__global__ __launch_bounds__(256) void k_sn_gram_head(const SnConv *convs, double *gram, int n, const ConvPrep *head,
-                                                     double *loss_acc, int *step) {
-    __shared__ float Ws[128][36];
-    if ((int)blockIdx.y >= n) {   // rows n, n + 1, ...: the planes
-        const int64_t b = (int64_t)(blockIdx.y - n) * gridDim.x + blockIdx.x;
-        if (b == 0 && threadIdx.x == 0) {   // a training step begins
-            *loss_acc = 0.0;
-            *step += 1;
-        }
-        conv_prep_body(*head, 1.0f, b * blockDim.x + threadIdx.x, (int64_t)(gridDim.y - n) * gridDim.x * blockDim.x);
-        return;
-    }
-    const SnConv cv = convs[blockIdx.y];
-    double *out = gram + (int64_t)blockIdx.y * kSnGramDoubles + (int64_t)kSnMaxDim * kSnMaxDim +
-                  (int64_t)blockIdx.x * kSnPairs * 256;
-    switch (threadIdx.x >> 6) {
-    case 0: sn_gram_body<0>(cv, Ws, out); break;
-    case 1: sn_gram_body<1>(cv, Ws, out); break;
-    case 2: sn_gram_body<2>(cv, Ws, out); break;
-    default: sn_gram_body<3>(cv, Ws, out); break;
-    }
-}
-
 int sn_launch(const SnConv *table_dev, int n, int64_t max_elems, double *gram, float *sigma, float *scale,
               float ln_lambda, bool apply, hipStream_t st, long long *prof = nullptr) {
     hipLaunchKernelGGL(k_sn_gram, dim3(kSnSplit, n), dim3(256), 0, st, table_dev, gram);
@@ -747,20 +738,6 @@ int sn_launch(const SnConv *table_dev, int n, int64_t max_elems, double *gram, f
     if (apply) hipLaunchKernelGGL(k_sn_apply, dim3(ew_blocks(max_elems, 256), n), dim3(kEw), 0, st, table_dev, scale);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
-}
-
-__global__ void k_es_init(lrs_es_state *st, int size, int patience) {
-    st->count = 0;
-    st->size = size;
-    st->patience = patience;
-    st->wait = 0;
-    st->stop = 0;
-    st->stop_epoch = -1;
-    st->best_epoch = 0;
-    st->reserved = 0;
-    st->best = INFINITY;
-    st->var_acc = 0.0;
-    st->last_var = NAN;
 }
 
 // cr: the update reads the interior of a framed output (N = C cr->H cr->W elements of it)
@@ -775,122 +752,6 @@ int es_update(const float *out, int64_t N, float *ring, lrs_es_state *es, hipStr
     hipLaunchKernelGGL(k_es_decide, dim3(1), dim3(64), 0, st, (const float *)ring, N, (int)nblk, es);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
-}
-
-inline uint64_t mix64(uint64_t z) {   // splitmix64 finaliser (host + device)
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-}
-
-__global__ void k_init_uniform(float *p, int64_t n, float bound, uint64_t key) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        uint64_t z = key + 0x9e3779b97f4a7c15ULL * (uint64_t)(i + 1);
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-        z ^= z >> 31;
-        const float u = (float)(z >> 40) * (1.0f / 16777216.0f);   // [0, 1)
-        p[i] = (2.0f * u - 1.0f) * bound;
-    }
-}
-
-__global__ void k_fill(float *p, int64_t n, float v) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        p[i] = v;
-}
-
-// img[b][i][j] = X[(i + H j) B + b] + c * L[...]   (…1-LiP.py:404; L nullable)
-__global__ void k_unfolded_to_image(const float *__restrict__ X, const float *__restrict__ L, float c, int64_t H,
-                                    int64_t W, int64_t B, float *__restrict__ img) {
-    const int64_t n = H * W * B;
-    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n; o += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t j = o % W, i = (o / W) % H, b = o / (W * H);
-        const int64_t src = (i + H * j) * B + b;
-        float v = X[src];
-        if (L) v = v + c * L[src];
-        img[o] = v;
-    }
-}
-
-// X[(i + H j) B + b] = img[b][i][j]   (…1-LiP.py:411)
-__global__ void k_image_to_unfolded(const float *__restrict__ img, int64_t H, int64_t W, int64_t B,
-                                    float *__restrict__ X) {
-    const int64_t n = H * W * B;
-    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n; o += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = o % B, p = o / B;
-        const int64_t i = p % H, j = p / H;
-        X[o] = img[(b * H + i) * W + j];
-    }
-}
-
-// ---- the same two transforms for an image inside a reflected frame (lrs_dipnet_set_frame) --------
-// The image's H x W pixels sit at (top, left) of a Hf x Wf frame.  For one image row i both kernels
-// transpose a 32 (columns j) x 32 (bands b) tile through LDS, so the unfolded rows X[(i + H j) B + b]
-// are read / written along b and the image rows along j.
-constexpr int kFrTile = 32;
-
-struct FrameGeom {
-    int H, W, B, top, left, Hf, Wf;
-};
-
-// The destinations of source index s along one axis of n pixels padded by lo before / hi after
-// (ReflectionPad2d: the edge is not repeated): itself at lo + s, its mirror image in the leading pad
-// (1 <= s <= lo) and in the trailing pad (n - 1 - hi <= s <= n - 2).  lo, hi < n.
-__device__ __forceinline__ int frame_dests(int s, int n, int lo, int hi, int d[3]) {
-    int nd = 0;
-    d[nd++] = lo + s;
-    if (s >= 1 && s <= lo) d[nd++] = lo - s;
-    if (s >= n - 1 - hi && s <= n - 2) d[nd++] = 2 * (n - 1) + lo - s;
-    return nd;
-}
-
-// img[b][top + i][left + j] = X[(i + H j) B + b] + c * L[...], and every frame pixel that reflects onto
-// (i, j) in the same pass: the whole [B][Hf][Wf] image is written once, the unfolded rows are read once.
-// grid (ceil(W / 32), ceil(B / 32), H), block (32, 8)
-__global__ __launch_bounds__(256) void k_unfolded_to_frame(const float *__restrict__ X, const float *__restrict__ L,
-                                                           float c, FrameGeom g, float *__restrict__ img) {
-    __shared__ float tile[kFrTile][kFrTile + 1];   // [j][b]
-    const int i = blockIdx.z, j0 = blockIdx.x * kFrTile, b0 = blockIdx.y * kFrTile;
-    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along b
-        const int j = j0 + r, b = b0 + threadIdx.x;
-        if (j < g.W && b < g.B) {
-            const int64_t src = ((int64_t)i + (int64_t)g.H * j) * g.B + b;
-            float v = X[src];
-            if (L) v = v + c * L[src];
-            tile[r][threadIdx.x] = v;
-        }
-    }
-    __syncthreads();
-    int ys[3];
-    const int ny = frame_dests(i, g.H, g.top, g.Hf - g.H - g.top, ys);
-    const int j = j0 + threadIdx.x;
-    if (j >= g.W) return;
-    int xs[3];
-    const int nx = frame_dests(j, g.W, g.left, g.Wf - g.W - g.left, xs);
-    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along j
-        const int b = b0 + r;
-        if (b >= g.B) break;
-        const float v = tile[threadIdx.x][r];
-        float *plane = img + (int64_t)b * g.Hf * g.Wf;
-        for (int a = 0; a < ny; ++a)
-            for (int e = 0; e < nx; ++e) plane[(int64_t)ys[a] * g.Wf + xs[e]] = v;
-    }
-}
-
-// X[(i + H j) B + b] = img[b][top + i][left + j]: the interior of the framed image, unfolded
-__global__ __launch_bounds__(256) void k_frame_to_unfolded(const float *__restrict__ img, FrameGeom g,
-                                                           float *__restrict__ X) {
-    __shared__ float tile[kFrTile][kFrTile + 1];   // [b][j]
-    const int i = blockIdx.z, j0 = blockIdx.x * kFrTile, b0 = blockIdx.y * kFrTile;
-    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along j
-        const int b = b0 + r, j = j0 + threadIdx.x;
-        if (b < g.B && j < g.W) tile[r][threadIdx.x] = img[((int64_t)b * g.Hf + g.top + i) * g.Wf + g.left + j];
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < kFrTile; r += blockDim.y) {   // lanes along b
-        const int j = j0 + r, b = b0 + threadIdx.x;
-        if (j < g.W && b < g.B) X[((int64_t)i + (int64_t)g.H * j) * g.B + b] = tile[threadIdx.x][r];
-    }
 }
 
 }  // namespace

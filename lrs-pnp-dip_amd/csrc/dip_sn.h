@@ -1,11 +1,13 @@
 // DIP low-rank prox, spectral norm: sigma_max of every conv weight (k_sn_gram, k_sn_gram_reduce,
-// k_sn_sigma) and W_bar / scale (k_sn_apply).  Part of dipnet.hip's translation unit: round_up,
+// k_sn_sigma), W_bar / scale (k_sn_apply) and the step head that joins the Gram partials with the first
+// conv's weight planes (k_sn_gram_head).  Part of dipnet.hip's translation unit: round_up,
 // wave_sum_butterfly and dpp_perm_f64 are lrs_common.h's.
 #pragma once
 #include <utility>
 
 #include "lrs_common.h"
 #include "lrs_dip.h"
+#include "dip_wprep.h"   // k_sn_gram_head's conv_prep_body
 
 namespace lrs {
 
@@ -470,3 +472,39 @@ __global__ void k_sn_apply(const SnConv *convs, const float *scale) {
 }
 
 }  // namespace lrs
+
+namespace {   // (internal linkage: this header is part of dipnet.hip's translation unit only)
+
+// The step head of the overlapped sigma (lrs_dipnet::sn_overlap): the spectral-norm Gram partials of
+// the n convs (blockIdx.y < n, k_sn_gram's body) and, in the extra rows blockIdx.y >= n, the first
+// conv's forward planes from the raw weights (the head ConvPrep, dip_wprep.h) with the step's loss
+// reset and Adam step count: one launch instead of two.
+// kHeadPlaneRows: the first conv's planes on 8 grid rows of kSnSplit workgroups (one row: the kernel took
+// 36.7 us, its 16 plane workgroups the longest; 8 rows: 19.2 us, 196^2 step 1.194 -> 1.177 ms, 3 interleaved
+// rounds, profiles/r06/ab/head_plane_rows.txt)
+constexpr int kHeadPlaneRows = 8;
+__global__ __launch_bounds__(256) void k_sn_gram_head(const lrs::SnConv *convs, double *gram, int n,
+                                                     const lrs::ConvPrep *head, double *loss_acc, int *step) {
+    using namespace lrs;
+    __shared__ float Ws[128][36];
+    if ((int)blockIdx.y >= n) {   // rows n, n + 1, ...: the planes
+        const int64_t b = (int64_t)(blockIdx.y - n) * gridDim.x + blockIdx.x;
+        if (b == 0 && threadIdx.x == 0) {   // a training step begins
+            *loss_acc = 0.0;
+            *step += 1;
+        }
+        conv_prep_body(*head, 1.0f, b * blockDim.x + threadIdx.x, (int64_t)(gridDim.y - n) * gridDim.x * blockDim.x);
+        return;
+    }
+    const SnConv cv = convs[blockIdx.y];
+    double *out = gram + (int64_t)blockIdx.y * kSnGramDoubles + (int64_t)kSnMaxDim * kSnMaxDim +
+                  (int64_t)blockIdx.x * kSnPairs * 256;
+    switch (threadIdx.x >> 6) {
+    case 0: sn_gram_body<0>(cv, Ws, out); break;
+    case 1: sn_gram_body<1>(cv, Ws, out); break;
+    case 2: sn_gram_body<2>(cv, Ws, out); break;
+    default: sn_gram_body<3>(cv, Ws, out); break;
+    }
+}
+
+}  // namespace

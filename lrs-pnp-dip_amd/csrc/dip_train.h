@@ -427,3 +427,21 @@ __global__ void k_es_decide(const float *ring, int64_t N, int nblk, lrs_es_state
 }
 
 }  // namespace lrs
+
+namespace {   // (internal linkage: this header is part of dipnet.hip's translation unit only)
+
+__global__ void k_es_init(lrs_es_state *st, int size, int patience) {
+    st->count = 0;
+    st->size = size;
+    st->patience = patience;
+    st->wait = 0;
+    st->stop = 0;
+    st->stop_epoch = -1;
+    st->best_epoch = 0;
+    st->reserved = 0;
+    st->best = INFINITY;
+    st->var_acc = 0.0;
+    st->last_var = NAN;
+}
+
+}  // namespace

@@ -45,7 +45,7 @@ inline ConvWs conv_ws(const ConvGeom &g, int Cout) {
     ConvWs w;
     w.dcol = plain_unit(g) ? 0 : (int64_t)g.Cin * g.k * g.k * g.Ho * g.Wo;
     w.part = conv_part_floats(g, Cout);
-    w.wpre_floats = (plain_unit(g) && !pw_ok(g, Cout)) ? 0 : (wprep_elems(g, Cout) + 7) / 2;
+    w.wpre_floats = (plain_unit(g) && !pw_ok(g, Cout)) ? 0 : (wprep_elems(g, Cout, false).total() + 7) / 2;
     return w;
 }
 
@@ -89,7 +89,9 @@ extern "C" int lrs_conv2d_bwd_f32(const float *gy, const float *col, const float
         return LRS_E_WORKSPACE;
     float *dc = cw.dcol ? (float *)ws : nullptr;
     float *pt = (float *)ws + cw.dcol;
-    return conv_bwd(g, gy, col, w, w_div, Cout, gx, gw, dc, pt, cw.part, (hipStream_t)stream);
+    rc = conv_wgrad(g, gy, col, w_div, Cout, gw, pt, cw.part, (hipStream_t)stream, false);
+    if (rc || !gx) return rc;
+    return conv_dgrad(g, gy, w, Cout, gx, dc, pt, cw.part, (hipStream_t)stream, 0, false, nullptr);
 }
 
 extern "C" int lrs_conv2d_bwd_x_f32(const float *gy, const float *x, const float *w, const float *w_div, int Cin,
@@ -107,8 +109,10 @@ extern "C" int lrs_conv2d_bwd_x_f32(const float *gy, const float *x, const float
     float *dc = cw.dcol ? (float *)ws : nullptr;
     float *pt = (float *)ws + cw.dcol;
     __bf16 *wp = cw.wpre_floats ? (__bf16 *)((float *)ws + cw.dcol + cw.part) : nullptr;
-    if (wp && gx && (rc = wprep(g, w, Cout, wp, wp + wprep_fwd_elems(g, Cout), (hipStream_t)stream))) return rc;
-    return conv_bwd(g, gy, x, w, w_div, Cout, gx, gw, dc, pt, cw.part, (hipStream_t)stream, 0, true, wp);
+    if (wp && gx && (rc = wprep(g, w, Cout, wp, wp + wprep_elems(g, Cout, false).fwd, (hipStream_t)stream))) return rc;
+    rc = conv_wgrad(g, gy, x, w_div, Cout, gw, pt, cw.part, (hipStream_t)stream, true);
+    if (rc || !gx) return rc;
+    return conv_dgrad(g, gy, w, Cout, gx, dc, pt, cw.part, (hipStream_t)stream, 0, true, wp);
 }
 
 extern "C" size_t lrs_bn_act_workspace(int C, int64_t P) {
@@ -501,8 +505,8 @@ int weight_grad(lrs_dipnet *net, int i, const float *x, hipStream_t ws, float *s
     case Wgrad::Gemm: break;
     }
     // explicit: on the node's col buffer; implicit (no col buffer): col^T gathered from the input
-    return conv_bwd(N.g, gz, N.col_off >= 0 ? net->f(N.col_off) : xin, cw.w, cw.div, N.C, nullptr, gw, nullptr, scratch,
-                    net->part_cap, ws, 0, N.col_off < 0, nullptr, wsplit_out, wt);
+    return conv_wgrad(N.g, gz, N.col_off >= 0 ? net->f(N.col_off) : xin, cw.div, N.C, gw, scratch, net->part_cap, ws,
+                      N.col_off < 0, wsplit_out, wt);
 }
 
 // pw (lrs_dipnet_train_steps): the input conv's weight gradient may leave its split-K partials for
@@ -591,13 +595,13 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
             switch (N.plan.dgrad) {
             case Dgrad::None: break;
             case Dgrad::Upc:   // by output parity class over the extended source grid, then the clamp fold
-                rc = upc_dgrad(N.g, gz, wp + wprep_fwd_elems(N.g, N.C, true), N.C, gx, net->f(net->dcol_off), part,
+                rc = upc_dgrad(N.g, gz, wp + wprep_elems(N.g, N.C, true).fwd, N.C, gx, net->f(net->dcol_off), part,
                                net->part_cap, st, written[t]);
                 break;
             case Dgrad::Adjoint: {   // gx = the adjoint gather of dL/dz on k_conv_sm, one GEMM
                 const auto &g = N.g;
                 const int kk = g.k * g.k, Cop = r16(N.C);
-                const SmPre la{wp + wprep_fwd_elems(g, N.C), (int64_t)g.Cin * kk * Cop, kk * Cop, g.Cin};
+                const SmPre la{wp + wprep_elems(g, N.C, false).fwd, (int64_t)g.Cin * kk * Cop, kk * Cop, g.Cin};
                 // the next node (t - 1 = i - 1, this tensor's only other writer would come before it)
                 // finishes the split-K sum inside its BN backward when that fits one workgroup
                 const bool fuse_next = t == i && !written[t] && net->nodes[t - 1].plan.bn_bwd_fuse;
@@ -612,9 +616,8 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
                 break;
             }
             case Dgrad::Gemm:
-                rc = conv_bwd(N.g, gz, N.col_off >= 0 ? net->f(N.col_off) : net->tensor(t, x), cw.w, cw.div, N.C, gx, nullptr,
-                              !plain_unit(N.g) ? net->f(net->dcol_off) : nullptr, part, net->part_cap, st, written[t],
-                              N.col_off < 0, wp);
+                rc = conv_dgrad(N.g, gz, cw.w, N.C, gx, !plain_unit(N.g) ? net->f(net->dcol_off) : nullptr, part,
+                                net->part_cap, st, written[t], N.col_off < 0, wp);
                 break;
             }
             if (rc) return rc;
@@ -859,7 +862,7 @@ extern "C" int lrs_dipnet_bind(lrs_dipnet *net, float *params, float *grads, flo
         const auto &N = net->nodes[i];
         if (N.d.kind != LRS_NODE_CONV || (N.sn_index < 0 && N.wpre_off < 0)) continue;
         __bf16 *wf = N.wpre_off >= 0 ? net->at<__bf16>(N.wpre_off) : nullptr;
-        __bf16 *wd = (wf && N.d.in0 > 0) ? wf + wprep_fwd_elems(N.g, N.C, N.upc) : nullptr;
+        __bf16 *wd = (wf && N.d.in0 > 0) ? wf + wprep_elems(N.g, N.C, N.upc).fwd : nullptr;
         prep.push_back(ConvPrep{params + N.w_off, N.sn_index >= 0 ? net->f(N.wn_off) : nullptr, wf, wd, N.C, N.g.Cin,
                                 N.g.k * N.g.k, r16(N.g.Cin), r16(N.C), N.sn_index, N.g.k,
                                 (wd && !N.sm && !N.upc) ? N.g.ke : 0, N.upc ? 1 : 0});

@@ -20,8 +20,8 @@ enum class BnFwd {    // BatchNorm + activation after the product
     Generic,          // bn_fwd (the activation alone for a conv without BatchNorm)
     ActInPw,          // a 1x1 without BatchNorm: the activation in k_pw's epilogue
 };
-enum class Dgrad { None, Upc, Adjoint, Gemm };   // none (reads the input) / upc_dgrad / SmAdj gather / conv_bwd
-enum class Wgrad { Table, Im2colGemm, Upc, Gemm };   // SmWgrad gather table / k_im2col + GEMM / upc_wgrad / conv_bwd
+enum class Dgrad { None, Upc, Adjoint, Gemm };   // none (reads the input) / upc_dgrad / SmAdj gather / conv_dgrad
+enum class Wgrad { Table, Im2colGemm, Upc, Gemm };   // SmWgrad gather table / k_im2col + GEMM / upc_wgrad / conv_wgrad
 
 struct NodePlan {   // of a conv node
     Fwd fwd = Fwd::Col;
@@ -264,17 +264,18 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
                 N.wn_off = ws.floats(N.C * N.Kc);
                 if (N.C * N.Kc > net->max_w) net->max_w = N.C * N.Kc;
             }
-            const bool planes_fit = wprep_elems(N.g, N.C) < INT32_MAX / 3;   // k_conv_prep's 32-bit plane indices
+            const int64_t planes = wprep_elems(N.g, N.C, false).total();
+            const bool planes_fit = planes < INT32_MAX / 3;   // k_conv_prep's 32-bit plane indices
             if (plain_unit(N.g)) {
                 if (net->implicit && pw_ok(N.g, N.C) && N.P >= kImplicitMinP && planes_fit)
-                    N.wpre_off = ws.planes(wprep_elems(N.g, N.C));   // 1x1 on k_pw: its pre-split weight planes
+                    N.wpre_off = ws.planes(planes);   // 1x1 on k_pw: its pre-split weight planes
             } else if (!(net->implicit && conv_implicit_ok(N.g, N.C) && N.P >= kImplicitMinP)) {
                 // col: the weight gradient's explicit im2col (written in the backward for a
                 // small-map conv, whose forward gathers it inside k_conv_sm)
                 N.col_off = ws.floats(N.Kc * N.P);
                 if (net->implicit && N.d.k <= 3 && conv_implicit_ok(N.g, N.C) && planes_fit) {
                     N.sm = true;
-                    N.wpre_off = ws.planes(wprep_elems(N.g, N.C));
+                    N.wpre_off = ws.planes(planes);
                     if (N.P <= kSmWgradOneLaunchP) {
                         N.wtab = sm_wgrad_table(N.g);
                         N.wtab_off = ws.floats((int64_t)N.wtab.size());
@@ -287,7 +288,7 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
                 }
             } else {
                 N.upc = upc_conv(N.g);
-                const int64_t elems = N.upc ? wprep_elems(N.g, N.C, true) : wprep_elems(N.g, N.C);
+                const int64_t elems = wprep_elems(N.g, N.C, N.upc).total();
                 if (elems >= INT32_MAX / 3) return LRS_E_UNSUPPORTED;
                 N.wpre_off = ws.planes(elems);
             }

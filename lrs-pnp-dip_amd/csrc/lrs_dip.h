@@ -1,5 +1,5 @@
 // Internal definitions shared by the DIP kernels (dip_kernels.h, dip_bn.h, dip_sn.h, dip_train.h, dip_gemm.h,
-// dip_sm.h, dip_dir.h), their launchers (dip_launch.h) and the engine (dipnet_plan.h, dipnet.hip).
+// dip_pw.h, dip_wprep.h, dip_dgrad.h, dip_sm.h, dip_dir.h), their launchers (dip_launch.h) and the engine (dipnet_plan.h, dipnet.hip).
 #pragma once
 #include "lrs_common.h"
 

@@ -6,7 +6,9 @@ same operands, in relative L2 and componentwise -- and never from the kernel, ru
 NaN-filled outputs, prints what it measured and asserts both metrics.  The f32-MFMA paths meet the same
 bound.  DESIGN.md 8.1 holds the rule, the measured values and the paths left out.
 
-Kernel and loader pair each conv case reaches (dip_launch.h conv_fwd / conv_bwd, dipnet_plan.h):
+Kernel and loader pair each conv case reaches (dip_launch.h conv_fwd / conv_wgrad / conv_dgrad, dipnet_plan.h;
+the kernels: dip_gemm.h k_gemm_s3 and its loaders, dip_pw.h k_pw, dip_dgrad.h the fold and border kernels,
+dip_sm.h k_conv_sm):
   conv primitives, col == NULL (lrs_conv2d_fwd_f32 / lrs_conv2d_bwd_x_f32):
     s3_reflect   3x3 reflection, stride 1, 19 x 21 (ragged 128-tiles).  fwd k_gemm_s3<LdPre, LdFwdTM>;
                  dgrad <LdPre, LdDgradTM> over the padded domain + k_fold_pad; wgrad <LdDense, LdWgradTM>

@@ -1,0 +1,80 @@
+"""One sha256 per output tensor of the DIP conv products, for bitwise A/B of two builds (LRSPNP_LIB).
+
+    python tools/conv_digest.py > new.txt
+    LRSPNP_LIB=.../liblrspnp_hip_parent.so python tools/conv_digest.py > parent.txt     # then diff
+
+Primitive ABI: every conv case of tests/test_gpu_dip.py (CONV_CASES) through lrs_conv2d_fwd_f32 and
+lrs_conv2d_bwd_f32 with a col buffer (split-bf16 and f32) and through lrs_conv2d_fwd_f32 and
+lrs_conv2d_bwd_x_f32 without one (upsample_dgrad 0 and 1): y, gw, gx.  Engine: three training steps
+from seed 0 on the 36 x 36 x 7 and 66 x 66 x 7 U-Nets and the 36 x 36 x 128 skip net, each with the
+default options, with upsample_dgrad = 1 and with precision = LRS_DIP_F32 (output, parameters,
+gradients): implicit and small-map paths, split-K with S > 1 and S = 1, the parity-class convs, and
+on the 66^2 net maps that are no multiple of 4.
+"""
+import ctypes
+import hashlib
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "..", "lrs-pnp-dip_amd"))
+sys.path.insert(0, os.path.join(HERE, "..", "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from lrspnp import _lib  # noqa: E402
+from lrspnp.dip import DipNet, lipschitz_unet_nodes, skip_nodes  # noqa: E402
+from test_gpu_dip import CONV_CASES, P, S  # noqa: E402
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+L = _lib.device_lib()
+for ci, case in enumerate(CONV_CASES):
+    cin, cout, H, W, k, stride, pad, pm, up = case
+    g = torch.Generator().manual_seed(ci)
+    x = torch.randn(cin, H, W, generator=g).cuda()
+    w = (torch.randn(cout, cin, k, k, generator=g) / np.sqrt(cin * k * k)).cuda()
+    b = (torch.randn(cout, generator=g) * 0.1).cuda()
+    Ho, Wo = ctypes.c_int(), ctypes.c_int()
+    assert L.lrs_conv2d_out_size(H, W, k, stride, pad, up, ctypes.byref(Ho), ctypes.byref(Wo)) == 0
+    gy = torch.randn(cout, Ho.value, Wo.value, generator=g).cuda()
+    div = torch.tensor([1.7], device="cuda")
+    ncol = L.lrs_conv2d_col_size(cin, H, W, k, stride, pad, up)
+    # (explicit, precision, upsample_dgrad)
+    for explicit, prec, ud in ((1, 1, 0), (1, 0, 0), (0, 1, 0), (0, 1, 1)):
+        opts = ctypes.byref(_lib.dip_opts(prec, ud))
+        nws = L.lrs_conv2d_workspace(cin, H, W, cout, k, stride, pad, up, opts)
+        ws = torch.zeros(nws // 4 + 1, device="cuda")
+        col = torch.zeros(max(ncol, 1), device="cuda")
+        y = torch.full((cout, Ho.value, Wo.value), float("nan"), device="cuda")
+        gw, gx = torch.full_like(w, float("nan")), torch.full_like(x, float("nan"))
+        geo = (cin, H, W, cout, k, stride, pad, pm, up)
+        rc = L.lrs_conv2d_fwd_f32(P(x), cin, H, W, P(w), P(b), cout, k, stride, pad, pm, up,
+                                  P(col) if explicit and ncol else None, P(y), opts, P(ws), nws, S())
+        if explicit:
+            rc2 = L.lrs_conv2d_bwd_f32(P(gy), P(col) if ncol else P(x), P(w), P(div), *geo, P(gx), P(gw), opts, P(ws), nws,
+                                       S())
+        else:
+            rc2 = L.lrs_conv2d_bwd_x_f32(P(gy), P(x), P(w), P(div), *geo, P(gx), P(gw), opts, P(ws), nws, S())
+        torch.cuda.synchronize()
+        tag = f"conv {ci} {'col' if explicit else 'implicit'} prec={prec} updgrad={ud} rc={rc},{rc2}"
+        for name, t in (("y", y), ("gw", gw), ("gx", gx)):
+            print(f"{tag} {name} {sha(t)}")
+
+for name, nodes, bands, hw in (("unet36x7", lipschitz_unet_nodes(7, 7, 128), 7, 36),
+                               ("unet66x7", lipschitz_unet_nodes(7, 7, 128), 7, 66),
+                               ("skip36x128", skip_nodes(128, 128), 128, 36)):
+    for oname, kw in (("default", {}), ("updgrad", {"upsample_dgrad": 1}), ("f32", {"precision": _lib.DIP_F32})):
+        net = DipNet(nodes, bands, hw, hw, **kw)
+        net.init_params(0)
+        g = torch.Generator(device="cuda").manual_seed(0)
+        x = torch.rand(bands, hw, hw, device="cuda", generator=g)
+        Co, Ho, Wo = net.out_shape   # (a size that is no multiple of 4 comes out larger than it went in)
+        t = torch.rand(Co, Ho, Wo, device="cuda", generator=g)
+        m = (torch.rand(Ho, Wo, device="cuda", generator=g) > 0.2).float()
+        net.train_steps(x, t, m, 3, use_graph=False)
+        torch.cuda.synchronize()
+        for k, v in (("output", net.output()), ("params", net.params), ("grads", net.grads), ("bnstats", net.bnstats)):
+            print(f"net {name} {oname} {k} {sha(v)}")

@@ -10,7 +10,7 @@
 #include <stdlib.h>
 
 #include "dip_kernels.h"
-#include "dip_gemm.h"
+#include "dip_dgrad.h"
 
 using namespace lrs;
 
