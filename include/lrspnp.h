@@ -105,11 +105,29 @@ int lrs_ista_alpha_f32(const float *D, int64_t n, int64_t K, const uint8_t *obs_
  *   max_workgroups: 0 (default) = one workgroup per 16-block tile; > 0 bounds the row-split
  *     kernel's grid (each workgroup then loops over tiles), so a concurrent launch on another
  *     stream (the DIP training of the …_DIP mains) keeps the rest of the CUs.  Results do not
- *     depend on it. */
+ *     depend on it.
+ *   accel: LRS_ISTA_ACCEL_NONE (0, default): the reference's ISTA above.  LRS_ISTA_ACCEL_FISTA: the
+ *     same gradient step and prox with Nesterov / FISTA momentum.  Start with x_0 (zero, or coefs
+ *     under warm_start), z_1 = x_0, t_1 = 1.  For k = 1..Nit:
+ *       x_k     = prox(z_k + D^T(obs .* (y - D z_k)) / alpha)
+ *       t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2
+ *       beta_k  = (t_k - 1) / t_{k+1}
+ *       z_{k+1} = x_k + beta_k (x_k - x_{k-1})
+ *     t and beta are computed in fp64 and beta is rounded once to float32; z is formed in float32.
+ *     The result is x_Nit, never z: the last iteration writes x itself back, and coefs and
+ *     phi = D x_Nit are formed from x_Nit.  alpha, the thresholds and the prox are unchanged.
+ *     beta_1 = 0, so Nit <= 2 is exactly the plain iteration.  Every path takes it (row-split,
+ *     generic, lrs_ista_pat_f32); the dictionary-resident kernels do not, so a call with accel at
+ *     their sizes (n_pad <= 64 with K = 256) runs the row-split kernel and needs its workspace
+ *     (lrs_ista_workspace with the same opts).  With warm_start = 1 the call starts from coefs with
+ *     the momentum reset (t = 1, x_prev = x_0): an accelerated run sliced over several calls does
+ *     NOT reproduce a single call, unlike the plain iteration.  Any other value: LRS_E_INVALID. */
 #define LRS_ISTA_F32 0
 #define LRS_ISTA_SPLIT_BF16 1
 #define LRS_ISTA_ALGO_AUTO 0
 #define LRS_ISTA_ALGO_GENERIC 1
+#define LRS_ISTA_ACCEL_NONE 0
+#define LRS_ISTA_ACCEL_FISTA 1
 typedef struct {
     int32_t precision;
     int32_t max_workgroups;
@@ -119,9 +137,12 @@ typedef struct {
     int32_t warm_start;   /* 1: start from x0 = coefs (on input) instead of 0 and write the result back to
                              coefs, so Nit iterations split over several calls give exactly the
                              iterates of one call (the time-sliced sparse coding beside the DIP, see
-                             DESIGN.md §5).  Row-split kernel only (n_pad > 64 or K != 256):
-                             LRS_E_UNSUPPORTED elsewhere or without coefs. */
-    int32_t reserved[4];
+                             DESIGN.md §5).  Row-split kernel only (n_pad > 64 or K != 256, or any
+                             K <= 512 with accel): LRS_E_UNSUPPORTED elsewhere or without coefs.
+                             With accel the momentum restarts in every call (see above). */
+    int32_t accel;        /* LRS_ISTA_ACCEL_NONE (0) or LRS_ISTA_ACCEL_FISTA (the first word that was
+                             reserved: callers that zeroed it run the plain iteration) */
+    int32_t reserved[3];
 } lrs_ista_opts;
 size_t lrs_ista_workspace(int64_t n, int64_t K, int prox, const lrs_ista_opts *opts);
 int lrs_ista_f32(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad,

@@ -846,10 +846,14 @@ static bool ista_use_generic(int64_t K, const lrs_ista_opts *opts) {
     return K > 512 || (opts && opts->algorithm == LRS_ISTA_ALGO_GENERIC);
 }
 
+// FISTA momentum (lrs_ista_opts.accel).  The resident kernels keep the coefficients in VGPRs for all
+// of Nit and have no accelerated form: a call with accel at their sizes runs the row-split kernel.
+static bool ista_accel(const lrs_ista_opts *opts) { return opts && opts->accel == LRS_ISTA_ACCEL_FISTA; }
+
 extern "C" size_t lrs_ista_workspace(int64_t n, int64_t K, int prox, const lrs_ista_opts *opts) {
     if (n <= 0 || K <= 0) return 0;
-    if (ista_use_generic(K, opts)) return ista_generic_workspace(n, K);
-    if (ista_resident(round_up(n, 16), K, prox)) return 0;
+    if (ista_use_generic(K, opts)) return ista_generic_workspace(n, K, ista_accel(opts));
+    if (ista_resident(round_up(n, 16), K, prox) && !ista_accel(opts)) return 0;
     return ista_rs_workspace(n, K);
 }
 
@@ -868,12 +872,14 @@ extern "C" int lrs_ista_f32(const float *Yb, const uint8_t *obs, const float *D,
     // warm start exists only on the row-split kernel: refuse it before any dispatch (the generic path
     // would otherwise restart from zero on every slice)
     const bool warm = opts && opts->warm_start;
-    if (warm && (!coefs || ista_use_generic(K, opts) || ista_resident(n_pad, K, prox))) return LRS_E_UNSUPPORTED;
+    const bool accel = ista_accel(opts);
+    const bool resident = ista_resident(n_pad, K, prox) && !accel;
+    if (warm && (!coefs || ista_use_generic(K, opts) || resident)) return LRS_E_UNSUPPORTED;
     if (ista_use_generic(K, opts))
-        return ista_generic(Yb, obs, D, n, n_pad, K, nb, alpha, thr, Nit, prox, coefs, phi, ws, ws_bytes, st);
-    if (!ista_resident(n_pad, K, prox))
+        return ista_generic(Yb, obs, D, n, n_pad, K, nb, alpha, thr, Nit, prox, coefs, phi, ws, ws_bytes, st, accel);
+    if (!resident)
         return ista_rs_launch(Yb, obs, D, n, n_pad, K, nb, alpha, thr, Nit, prox, coefs, phi, ws, ws_bytes, max_wg, st,
-                              warm ? coefs : nullptr);
+                              warm ? coefs : nullptr, accel);
     IstaParams p{Yb, obs, D, alpha, thr, coefs, phi, (int)n, (int)n_pad, Nit, prox, nb, 7.0};
     const int64_t blocks_per_wg = (int64_t)kIstaWaves * 16;
     dim3 grid((unsigned)((nb + blocks_per_wg - 1) / blocks_per_wg));

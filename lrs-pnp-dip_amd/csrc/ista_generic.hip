@@ -95,6 +95,16 @@ __global__ void k_gen_soft(const float *__restrict__ G, float *__restrict__ X, c
     }
 }
 
+// FISTA momentum (lrs_ista_opts.accel): X holds x_k after the prox; X <- z_{k+1} = x_k + beta (x_k - x_{k-1}),
+// Xprev <- x_k.  beta = 0 (the first iteration) leaves X as it is.
+__global__ void k_gen_momentum(float *__restrict__ X, float *__restrict__ Xprev, float beta, int64_t total) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const float xn = X[i];
+        if (beta != 0.f) X[i] = xn + beta * (xn - Xprev[i]);
+        Xprev[i] = xn;
+    }
+}
+
 __global__ void k_gen_phi(const float *__restrict__ R, float *__restrict__ phi, int64_t rows, int n, int n_pad) {
     const int64_t total = rows * n_pad;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -116,23 +126,25 @@ static int64_t ista_generic_part_floats(int64_t n, int64_t K) {
     return m;
 }
 
-size_t ista_generic_workspace(int64_t n, int64_t K) {
+size_t ista_generic_workspace(int64_t n, int64_t K, bool accel) {
     const int64_t c = kGenChunk;
-    return (size_t)(2 * c * K + c * n + ista_generic_part_floats(n, K)) * sizeof(float) + 256;
+    return (size_t)((accel ? 3 : 2) * c * K + c * n + ista_generic_part_floats(n, K)) * sizeof(float) + 256;
 }
 
 int ista_generic(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
                  const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
-                 size_t ws_bytes, hipStream_t st) {
-    if (!ws || ws_bytes < ista_generic_workspace(n, K)) return LRS_E_WORKSPACE;
+                 size_t ws_bytes, hipStream_t st, bool accel) {
+    if (!ws || ws_bytes < ista_generic_workspace(n, K, accel)) return LRS_E_WORKSPACE;
     if (n > INT32_MAX / 2 || K > 16384) return LRS_E_UNSUPPORTED;
     const int64_t c = kGenChunk;
     float *X = (float *)ws, *G = X + c * K, *R = G + c * K, *part = R + c * n;
     const int64_t part_cap = ista_generic_part_floats(n, K);
+    float *Xprev = part + part_cap;   // x_{k-1} (accel only: the workspace is that much longer)
     for (int64_t j0 = 0; j0 < nb; j0 += c) {
         const int rows = (int)std::min(c, nb - j0);
         hipError_t e = hipMemsetAsync(X, 0, sizeof(float) * rows * K, st);
         if (e != hipSuccess) return (int)e;
+        double tk = 1.0;   // FISTA t_k (fp64, as the fused kernels)
         for (int it = 0; it < Nit; ++it) {
             int rc = dense_gemm(0, 1, X, D, R, rows, (int)n, (int)K, part, part_cap, st);   // R = X D^T
             if (rc) return rc;
@@ -151,6 +163,14 @@ int ista_generic(const float *Yb, const uint8_t *obs, const float *D, int64_t n,
             } else {
                 rc = nlm_col_launch(G, K, X, K, K, rows, 0.0, thr + j0, st);
                 if (rc) return rc;
+            }
+            if (accel) {
+                const double tn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * tk * tk));
+                const float beta = (float)((tk - 1.0) / tn);
+                tk = tn;
+                if (it + 1 < Nit)   // the last iteration leaves x_Nit itself
+                    hipLaunchKernelGGL(k_gen_momentum, dim3(gen_blocks(rows * K)), dim3(256), 0, st, X, Xprev, beta,
+                                       (int64_t)rows * K);
             }
             LRS_CHECK_LAUNCH();
         }

@@ -121,7 +121,9 @@ struct IstaPatParams {
 __host__ __device__ constexpr size_t pat_lds_bytes(int NQ) { return (size_t)NQ * 2048; }
 
 // WPE: waves per SIMD the registers are bounded for (2: one 512-thread workgroup per CU; 4: two)
-template <int NQ, int S, int WPE = 2>
+// ACCEL (lrs_ista_opts.accel = LRS_ISTA_ACCEL_FISTA): as k_ista_rs (ista_rs.hip): xbuf holds z_k, the
+// owner of an atom tile keeps x_{k-1} in VGPRs and rewrites its tiles with z_{k+1} after the prox.
+template <int NQ, int S, bool ACCEL, int WPE = 2>
 __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
     static_assert(NQ % S == 0, "atom tiles split evenly over the waves");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -226,6 +228,8 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
         for (int k = 0; k < RING; ++k) ring[k] = qfrag(k);
         __syncthreads();   // x0 in LDS
 
+        floatx4 xold[ACCEL ? NOWN : 1];   // x_{k-1} of the owned atom tiles (ACCEL only)
+        double tk = 1.0;                  // t_k; beta_1 = 0, so xold needs no start value
         for (int it = 0; it < p.Nit; ++it) {
             floatx4 acc[NOWN];
 #pragma unroll
@@ -282,6 +286,20 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
                 xbuf[q * 64 + lane] = floatx4{a0 < K ? o[0] : 0.f, a0 + 1 < K ? o[1] : 0.f, a0 + 2 < K ? o[2] : 0.f,
                                               a0 + 3 < K ? o[3] : 0.f};
             }
+            if constexpr (ACCEL) {
+                // ---- momentum on the owned tiles: xbuf <- z_{k+1}, but x_Nit itself after the last prox ----
+                const double tn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * tk * tk));
+                const float beta = (float)((tk - 1.0) / tn);
+                tk = tn;
+                const bool mom = it > 0 && it + 1 < p.Nit;
+#pragma unroll
+                for (int o = 0; o < NOWN; ++o) {
+                    const int q = w + S * o;
+                    const floatx4 xn = xbuf[q * 64 + lane];
+                    if (mom) xbuf[q * 64 + lane] = xn + beta * (xn - xold[o]);
+                    xold[o] = xn;
+                }
+            }
             __syncthreads();
         }
 
@@ -332,13 +350,13 @@ size_t ista_pat_workspace(int64_t n, int64_t K, int64_t npat) {
 
 // Waves per workgroup: 8 for K > 128 (configs[2] sparse coding alone: 2.00 ms vs 2.10 ms with 4;
 // profiles/r04/ista_pat/), 4 below (one or two atom tiles per wave).
-template <int NQ, int S, int WPE = 2>
+template <int NQ, int S, bool ACCEL, int WPE = 2>
 static int launch_pat_k(const IstaPatParams &p, int64_t max_wg, hipStream_t st) {
     static std::atomic<uint64_t> opted{0};   // per device
-    if (const int rc = lds_opt_in((const void *)k_ista_pat<NQ, S, WPE>, 160 * 1024, opted)) return rc;
+    if (const int rc = lds_opt_in((const void *)k_ista_pat<NQ, S, ACCEL, WPE>, 160 * 1024, opted)) return rc;
     int64_t grid = p.ntiles;
     if (max_wg > 0 && grid > max_wg) grid = max_wg;
-    hipLaunchKernelGGL((k_ista_pat<NQ, S, WPE>), dim3((unsigned)grid), dim3(64 * S), pat_lds_bytes(NQ), st, p);
+    hipLaunchKernelGGL((k_ista_pat<NQ, S, ACCEL, WPE>), dim3((unsigned)grid), dim3(64 * S), pat_lds_bytes(NQ), st, p);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
@@ -370,7 +388,7 @@ int ista_pat_prepare(const float *D, int64_t n, int64_t K, const uint8_t *obs_pa
 int ista_pat_launch(const float *Yb, const uint8_t *obs_pat, int64_t npat, const int32_t *plan, int64_t ntiles,
                     int64_t n, int64_t n_pad, int64_t K, int64_t nb, const float *alpha, const double *thr, int Nit,
                     int prox, float *coefs, float *phi, void *ws, size_t ws_bytes, int64_t max_wg, hipStream_t st,
-                    const float *x0) {
+                    const float *x0, bool accel) {
     if (K < 1 || K > 512) return LRS_E_UNSUPPORTED;
     if (!ws || ws_bytes < (size_t)pat_images_floats(n_pad, K, npat) * sizeof(float)) return LRS_E_WORKSPACE;
     const int NQ = ista_nq(K);
@@ -384,9 +402,17 @@ int ista_pat_launch(const float *Yb, const uint8_t *obs_pat, int64_t npat, const
     IstaPatParams p{Yb, obs_pat, plan, DAf, DTf, QAf, alpha, thr, coefs, phi, x0, (int)n_pad, (int)K, Nit, prox,
                     nb, ntiles, npat, 7.0};
     const int waves = NQ >= 16 ? 8 : 4;
+    if (accel) {
+        switch (NQ) {
+        case 4: return launch_pat_k<4, 4, true>(p, max_wg, st);
+        case 8: return launch_pat_k<8, 4, true>(p, max_wg, st);
+        case 16: return launch_pat_k<16, 8, true>(p, max_wg, st);
+        default: return launch_pat_k<32, 8, true>(p, max_wg, st);
+        }
+    }
     switch (NQ) {
-    case 4: return launch_pat_k<4, 4>(p, max_wg, st);
-    case 8: return launch_pat_k<8, 4>(p, max_wg, st);
+    case 4: return launch_pat_k<4, 4, false>(p, max_wg, st);
+    case 8: return launch_pat_k<8, 4, false>(p, max_wg, st);
     case 16:
         // 8 waves, registers unbounded (192, one workgroup per CU).  The 128-register bound (two
         // workgroups per CU; WPE = 4) is bit-identical and a little faster
@@ -394,8 +420,8 @@ int ista_pat_launch(const float *Yb, const uint8_t *obs_pat, int64_t npat, const
         // the configs[2] bench 7.87 either way, profiles/r04/ista_pat_wpe/), but spills 37 registers
         // (152 B of scratch per lane, 29 with a 2-deep ring): the PMC pass then measured 1.26 GB of
         // fabric traffic per configs[2] launch instead of 122 MB (profiles/r04/ista_pat_spill/).
-        return waves == 8 ? launch_pat_k<16, 8>(p, max_wg, st) : launch_pat_k<16, 4>(p, max_wg, st);
-    default: return launch_pat_k<32, 8>(p, max_wg, st);
+        return waves == 8 ? launch_pat_k<16, 8, false>(p, max_wg, st) : launch_pat_k<16, 4, false>(p, max_wg, st);
+    default: return launch_pat_k<32, 8, false>(p, max_wg, st);
     }
 }
 
@@ -463,5 +489,6 @@ extern "C" int lrs_ista_pat_f32(const float *Yb, const uint8_t *obs_pat, int64_t
     if (K > 512) return LRS_E_UNSUPPORTED;
     if (nb == 0) return LRS_OK;
     return lrs::ista_pat_launch(Yb, obs_pat, npat, plan, ntiles, n, n_pad, K, nb, alpha, thr, Nit, prox, coefs, phi, ws,
-                                ws_bytes, max_wg, (hipStream_t)stream, warm ? coefs : nullptr);
+                                ws_bytes, max_wg, (hipStream_t)stream, warm ? coefs : nullptr,
+                                opts && opts->accel == LRS_ISTA_ACCEL_FISTA);
 }

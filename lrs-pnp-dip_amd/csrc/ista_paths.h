@@ -20,6 +20,7 @@ inline int ista_check_args(int64_t n, int64_t n_pad, int64_t K, int64_t nb, int 
     if (opts->precision != LRS_ISTA_F32 && opts->precision != LRS_ISTA_SPLIT_BF16) return LRS_E_INVALID;
     if (opts->max_workgroups < 0) return LRS_E_INVALID;
     if (opts->warm_start != 0 && opts->warm_start != 1) return LRS_E_INVALID;
+    if (opts->accel != LRS_ISTA_ACCEL_NONE && opts->accel != LRS_ISTA_ACCEL_FISTA) return LRS_E_INVALID;
     return LRS_OK;
 }
 
@@ -29,16 +30,17 @@ size_t ista_rs_workspace(int64_t n, int64_t K);
 int ista_rs_images(const float *D, int64_t n, int64_t K, int NT, int NQ, float4 *DAf, float4 *DTf, hipStream_t st);
 int ista_rs_launch(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
                    const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
-                   size_t ws_bytes, int64_t max_wg, hipStream_t st, const float *x0);
+                   size_t ws_bytes, int64_t max_wg, hipStream_t st, const float *x0, bool accel);
 // NLmeansfilter(g, 3, 3, h) of nvec columns of length K (the MATLAB-variant prox)
 int nlm_matlab_col_launch(const float *g, int64_t ldg, float *out, int64_t ldo, int64_t K, int64_t nvec, double h,
                           const double *h_per_vec, hipStream_t st);
 
 // ---- ista_generic.hip: the dense-GEMM path (any K; the only one for K > 512) -------------------
-size_t ista_generic_workspace(int64_t n, int64_t K);
+// accel: one more chunk of coefficients (x_{k-1}) behind the plain layout
+size_t ista_generic_workspace(int64_t n, int64_t K, bool accel);
 int ista_generic(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
                  const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
-                 size_t ws_bytes, hipStream_t st);
+                 size_t ws_bytes, hipStream_t st, bool accel);
 
 // ---- dipnet.hip: C = op(A) op(B), fp32-accurate, split-K partials in `part` --------------------
 int64_t dense_gemm_part_floats(int M, int N, int K);

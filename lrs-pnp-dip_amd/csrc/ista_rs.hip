@@ -55,12 +55,29 @@ struct IstaRsParams {
 //   part  [NQ atom tiles][S-1 partial G images][64]     (S = 1: none)
 //   xbuf  [NQ][64]            the coefficients x: B operand of every R_t, rewritten by the prox
 //   gbuf  [16 blocks][NQ*16]  the gradient rows read by the prox (chunk index XOR-swizzled by block)
-__host__ __device__ constexpr size_t rs_lds_bytes(int NQ, int S) { return (size_t)(S + 1) * NQ * 1024; }
+//   xoldl [NQ][64]           ACCEL with S = 1 only: x_{k-1} (see k_ista_rs)
+__host__ __device__ constexpr size_t rs_lds_bytes(int NQ, int S, bool accel = false) {
+    return (size_t)(S + 1 + (accel && S == 1 ? 1 : 0)) * NQ * 1024;
+}
+
+// Waves per SIMD the registers of k_ista_rs<NQ, ., S, ACCEL> are bounded for: 2 up to K = 256, 1 above.
+// The accelerated K = 256 forms with fewer than 4 waves hold 32 or more registers of x_{k-1} beside
+// the 64 of G and spill at the 256-register bound (40 B of scratch per lane at S = 2, 12 B at S = 3), so
+// those alone are bounded for 1.
+constexpr int rs_minw(int NQ, int S, bool accel) { return NQ == 32 || (accel && NQ == 16 && S < 4) ? 1 : 2; }
 
 // The observation term is split off the residual: D^T (m .* (y - D x)) = b - D^T (m .* D x) with
 // b = D^T (m .* y) formed once per launch (each owner keeps its atom tiles of b in VGPRs), so the
 // inner iterations never re-read y: per row tile they need D (L2), x (LDS) and 4 mask bits (VGPR).
-template <int NQ, int MINW, int S>
+//
+// ACCEL (lrs_ista_opts.accel = LRS_ISTA_ACCEL_FISTA): xbuf holds the extrapolated point z_k instead
+// of x_k.  The prox leaves x_k in xbuf; its owner then rewrites its own tiles (the same lane wrote
+// them, so no barrier in between) with z_{k+1} = x_k + beta_k (x_k - x_{k-1}), x_{k-1} kept in VGPRs
+// (xold, 4 floats per owned atom tile).  The single-row-tile form (S = 1), whose one wave owns all NQ
+// tiles, has no 4 NQ registers left and keeps x_{k-1} in LDS (xoldl; each lane reads back only what it
+// wrote).  t_k (fp64) and beta_k (rounded once to float32) are wave-uniform.  The last iteration
+// leaves x_Nit itself, so the outputs read xbuf as before.
+template <int NQ, int MINW, int S, bool ACCEL>
 __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KP = NQ * 16;
@@ -227,6 +244,10 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
         }
     };
 
+    constexpr bool XOLD_LDS = ACCEL && S == 1;
+    floatx4 xold[ACCEL && !XOLD_LDS ? NOWN : 1];   // x_{k-1} of the owned atom tiles (ACCEL only)
+    floatx4 *xoldl = reinterpret_cast<floatx4 *>(gbuf + 16 * KP);
+    double tk = 1.0;                  // t_k; beta_1 = 0, so x_{k-1} needs no start value
     for (int it = 0; it < p.Nit; ++it) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) G[q] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -275,6 +296,30 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
             }
             xbuf[q * 64 + lane] = floatx4{a0 < K ? o[0] : 0.f, a0 + 1 < K ? o[1] : 0.f, a0 + 2 < K ? o[2] : 0.f,
                                           a0 + 3 < K ? o[3] : 0.f};
+        }
+        if constexpr (ACCEL) {
+            // ---- momentum on the owned tiles: xbuf <- z_{k+1}, but x_Nit itself after the last prox ----
+            const double tn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * tk * tk));
+            const float beta = (float)((tk - 1.0) / tn);
+            tk = tn;
+            const bool mom = it > 0 && it + 1 < p.Nit;
+            if constexpr (XOLD_LDS) {
+#pragma unroll 1
+                for (int q = 0; q < NQ; ++q) {
+                    const floatx4 xn = xbuf[q * 64 + lane];
+                    if (mom) xbuf[q * 64 + lane] = xn + beta * (xn - xoldl[q * 64 + lane]);
+                    xoldl[q * 64 + lane] = xn;
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    if (w == q % S) {
+                        const floatx4 xn = xbuf[q * 64 + lane];
+                        if (mom) xbuf[q * 64 + lane] = xn + beta * (xn - xold[q / S]);
+                        xold[q / S] = xn;
+                    }
+                }
+            }
         }
         __syncthreads();
     }
@@ -384,26 +429,31 @@ static int rs_pick_waves(int64_t tiles, int NT, int NQ, int minw) {
     return best;
 }
 
-template <int NQ, int MINW, int S>
+template <int NQ, int S, bool ACCEL>
 static int launch_rs_k(const IstaRsParams &p, int64_t max_wg, hipStream_t st) {
+    constexpr int MINW = rs_minw(NQ, S, ACCEL);
     int64_t tiles = (p.nb + 15) / 16;
     if (max_wg > 0 && tiles > max_wg) tiles = max_wg;
     static std::atomic<uint64_t> opted{0};   // dynamic LDS beyond 64 KiB, per device
-    if (const int rc = lds_opt_in((const void *)k_ista_rs<NQ, MINW, S>, 160 * 1024, opted)) return rc;
-    const size_t lds = rs_lds_bytes(NQ, S);
-    hipLaunchKernelGGL((k_ista_rs<NQ, MINW, S>), dim3((unsigned)tiles), dim3(64 * S), lds, st, p);
+    if (const int rc = lds_opt_in((const void *)k_ista_rs<NQ, MINW, S, ACCEL>, 160 * 1024, opted)) return rc;
+    const size_t lds = rs_lds_bytes(NQ, S, ACCEL);
+    hipLaunchKernelGGL((k_ista_rs<NQ, MINW, S, ACCEL>), dim3((unsigned)tiles), dim3(64 * S), lds, st, p);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
 
-template <int NQ, int MINW>
+template <int NQ, bool ACCEL>
 static int launch_rs(const IstaRsParams &p, int NT, int64_t max_wg, hipStream_t st) {
     const int64_t tiles = (p.nb + 15) / 16;
-    switch (rs_pick_waves(tiles, NT, NQ, MINW)) {
-    case 1: return launch_rs_k<NQ, MINW, 1>(p, max_wg, st);
-    case 2: return launch_rs_k<NQ, MINW, 2>(p, max_wg, st);
-    case 3: return launch_rs_k<NQ, MINW, 3>(p, max_wg, st);
-    default: return launch_rs_k<NQ, MINW, 4>(p, max_wg, st);
+    int S = rs_pick_waves(tiles, NT, NQ, rs_minw(NQ, 4, false));   // the plain kernel's choice
+    // the accelerated K = 256 forms with 2 or 3 waves are bounded for one wave per SIMD (rs_minw); the
+    // 4-wave form keeps two, which measured faster wherever the rows allow it
+    if (ACCEL && NQ == 16 && S < 4 && NT >= 4) S = 4;
+    switch (S) {
+    case 1: return launch_rs_k<NQ, 1, ACCEL>(p, max_wg, st);
+    case 2: return launch_rs_k<NQ, 2, ACCEL>(p, max_wg, st);
+    case 3: return launch_rs_k<NQ, 3, ACCEL>(p, max_wg, st);
+    default: return launch_rs_k<NQ, 4, ACCEL>(p, max_wg, st);
     }
 }
 
@@ -418,7 +468,7 @@ int ista_rs_images(const float *D, int64_t n, int64_t K, int NT, int NQ, float4 
 
 int ista_rs_launch(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
                    const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
-                   size_t ws_bytes, int64_t max_wg, hipStream_t st, const float *x0) {
+                   size_t ws_bytes, int64_t max_wg, hipStream_t st, const float *x0, bool accel) {
     if (K < 1 || K > 512) return LRS_E_UNSUPPORTED;
     const int NQ = ista_nq(K);
     const int NT = (int)(n_pad / 16);
@@ -431,11 +481,19 @@ int ista_rs_launch(const float *Yb, const uint8_t *obs, const float *D, int64_t 
     float4 *DTf = DAf + (size_t)NT * NQ * 64;
     if (const int rc = ista_rs_images(D, n, K, NT, NQ, DAf, DTf, st)) return rc;
     IstaRsParams p{Yb, obs, DAf, DTf, alpha, thr, coefs, phi, (int)n_pad, (int)K, Nit, prox, nb, 7.0, x0};
+    if (accel) {
+        switch (NQ) {
+        case 4: return launch_rs<4, true>(p, NT, max_wg, st);
+        case 8: return launch_rs<8, true>(p, NT, max_wg, st);
+        case 16: return launch_rs<16, true>(p, NT, max_wg, st);
+        default: return launch_rs<32, true>(p, NT, max_wg, st);
+        }
+    }
     switch (NQ) {
-    case 4: return launch_rs<4, 2>(p, NT, max_wg, st);
-    case 8: return launch_rs<8, 2>(p, NT, max_wg, st);
-    case 16: return launch_rs<16, 2>(p, NT, max_wg, st);
-    default: return launch_rs<32, 1>(p, NT, max_wg, st);
+    case 4: return launch_rs<4, false>(p, NT, max_wg, st);
+    case 8: return launch_rs<8, false>(p, NT, max_wg, st);
+    case 16: return launch_rs<16, false>(p, NT, max_wg, st);
+    default: return launch_rs<32, false>(p, NT, max_wg, st);
     }
 }
 

@@ -30,6 +30,8 @@ DIP_F32, DIP_SPLIT_BF16 = 0, 1
 
 
 ISTA_ALGO_AUTO, ISTA_ALGO_GENERIC = 0, 1
+ISTA_ACCEL_NONE, ISTA_ACCEL_FISTA = 0, 1
+ISTA_ACCEL = {"off": ISTA_ACCEL_NONE, "fista": ISTA_ACCEL_FISTA}
 
 # flag word (`warm`) of the SVT calls
 SVT_WARM, SVT_JACOBI, SVT_MULTI_WG, SVT_WIDE_TRI, SVT_WIDE_MW = 1, 2, 4, 8, 16
@@ -37,7 +39,7 @@ SVT_WARM, SVT_JACOBI, SVT_MULTI_WG, SVT_WIDE_TRI, SVT_WIDE_MW = 1, 2, 4, 8, 16
 
 class IstaOpts(ctypes.Structure):
     _fields_ = [("precision", ctypes.c_int32), ("max_workgroups", ctypes.c_int32), ("algorithm", ctypes.c_int32),
-                ("warm_start", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
+                ("warm_start", ctypes.c_int32), ("accel", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
 class DipOpts(ctypes.Structure):
@@ -45,8 +47,16 @@ class DipOpts(ctypes.Structure):
 
 
 def ista_opts(precision: int = ISTA_SPLIT_BF16, max_workgroups: int = 0, algorithm: int = ISTA_ALGO_AUTO,
-              warm_start: int = 0) -> IstaOpts:
-    return IstaOpts(precision=precision, max_workgroups=max_workgroups, algorithm=algorithm, warm_start=warm_start)
+              warm_start: int = 0, accel: int = ISTA_ACCEL_NONE) -> IstaOpts:
+    return IstaOpts(precision=precision, max_workgroups=max_workgroups, algorithm=algorithm, warm_start=warm_start,
+                    accel=accel)
+
+
+def ista_accel(name) -> int:
+    """lrs_ista_opts.accel for "off" | "fista" (anything else is refused here, before any call)."""
+    if name not in ISTA_ACCEL:
+        raise LrsError(f"unknown accel {name!r} ({' | '.join(ISTA_ACCEL)})")
+    return ISTA_ACCEL[name]
 
 
 def dip_opts(precision: int = DIP_SPLIT_BF16, upsample_dgrad: int = 0) -> DipOpts:

@@ -22,6 +22,11 @@ Warm start.  From the second round on the sparse coding continues from the previ
 coefficients where the kernel can (``lrs_ista_opts.warm_start``): the row-split kernel of
 ``lrs_ista_f32`` (n_pad > 64 or K != 256) and the per-pattern kernel of ``lrs_ista_pat_f32``.  The
 dictionary-resident kernels (n_pad <= 64 with K = 256) start every round from zero.
+
+``DictLearnConfig.accel = "fista"`` runs every round's sparse coding with Nesterov momentum
+(``lrs_ista_opts.accel``).  The warm start between rounds then carries the coefficients only: the
+momentum restarts in every call, which is the right thing after D has changed.  Accelerated calls
+run the row-split kernel at the resident sizes too, so they warm-start at every K <= 512.
 """
 from __future__ import annotations
 
@@ -45,12 +50,14 @@ class DictLearnConfig:
     rounds: int = 20                 # sparse coding + dictionary step
     n_inner: int = 10                # majorisation-minimisation iterations per dictionary step
     normalise: bool = True           # unit-norm columns at the end (columnNormalise.m)
+    accel: str = "off"               # per-round sparse coding: "off" (ISTA) or "fista" (lrs_ista_opts.accel)
     seed: int = 0
 
 
-def warm_start_supported(n_pad: int, K: int, per_pattern: bool) -> bool:
-    """Whether the sparse-coding kernel these sizes select continues from given coefficients."""
-    return per_pattern or n_pad > 64 or K != 256
+def warm_start_supported(n_pad: int, K: int, per_pattern: bool, accel: str = "off") -> bool:
+    """Whether the sparse-coding kernel these sizes select continues from given coefficients
+    (accelerated calls never run the resident kernels)."""
+    return per_pattern or n_pad > 64 or K != 256 or accel != "off"
 
 
 def training_blocks(Y, M, cfg: DictLearnConfig, rng):
@@ -114,13 +121,15 @@ def learn_blocks(Yb, obs, n: int, D0, cfg: DictLearnConfig):
     obs_pat = t(np.unpackbits(uniq, axis=1)[:, :n_pad].astype(np.uint8))
     inv_d = t(inv.astype(np.int64))
     per_pattern = K <= 512 and ops.ista_pat_preferred(n, K, nb, npat, cfg.Nit)   # the solver's own rule
-    warm_ok = warm_start_supported(n_pad, K, per_pattern)
+    if cfg.accel not in ("off", "fista"):
+        raise LrsError(f"unknown accel {cfg.accel!r} (off | fista)")
+    warm_ok = warm_start_supported(n_pad, K, per_pattern, cfg.accel)
     if per_pattern:
         plan, ntiles = ops.ista_pat_plan(inv, npat)
         plan_d = t(plan)
         ista_ws = ops.ista_pat_workspace(n, K, npat, dev)
     else:
-        ista_ws = ops.ista_workspace(n, K, ops.PROX_SOFT, dev)
+        ista_ws = ops.ista_workspace(n, K, ops.PROX_SOFT, dev, accel=cfg.accel)
     coefs = torch.zeros((nb, K), dtype=torch.float32, device=dev)
     phi = torch.empty((nb, n_pad), dtype=torch.float32, device=dev)
     H = torch.empty((K, K), dtype=torch.float32, device=dev)
@@ -136,10 +145,10 @@ def learn_blocks(Yb, obs, n: int, D0, cfg: DictLearnConfig):
         if per_pattern:
             ops.ista_pat_prepare(D, obs_pat, n, ws=ista_ws)
             ops.ista_pat(Yb, obs_pat, plan_d, ntiles, K, n, alpha, thr, cfg.Nit, ista_ws, ops.PROX_SOFT, phi=phi,
-                         coefs=coefs, want_coefs=True, warm_start=warm)
+                         coefs=coefs, want_coefs=True, warm_start=warm, accel=cfg.accel)
         else:
             ops.ista(Yb, obs, D, n, alpha, thr, cfg.Nit, ops.PROX_SOFT, phi=phi, coefs=coefs, want_coefs=True,
-                     ws=ista_ws, warm_start=warm)
+                     ws=ista_ws, warm_start=warm, accel=cfg.accel)
         ops.dict_stats(coefs, H=H, c=c, ws=ws)
         ops.dict_update(Yb, obs, coefs, D, n, c, n_inner, obj=history[r], ws=ws)
     if cfg.normalise:

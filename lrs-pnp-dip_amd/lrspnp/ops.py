@@ -12,7 +12,7 @@ import torch
 
 from . import _lib as _libmod
 from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLAB, PROX_SOFT, SVT_JACOBI, SVT_MULTI_WG,
-                   SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, LrsError, check, device_lib, lib)
+                   SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, LrsError, check, device_lib, ista_accel, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
            "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
@@ -118,23 +118,28 @@ def ista_alpha(D, obs_pat, n: int, mode: int, lambda_ista: float, stream=None):
     return alpha, thr
 
 
-def ista_workspace(n: int, K: int, prox: int, device, algorithm: int = 0) -> torch.Tensor | None:
+def ista_workspace(n: int, K: int, prox: int, device, algorithm: int = 0, accel: str = "off") -> torch.Tensor | None:
     """Device workspace of lrs_ista_f32 (the row-split kernel's fragment-ordered dictionary images,
     or the generic path's chunk buffers for K > 512); None when the dictionary-resident kernels serve
-    (n <= 64, K = 256, skimage / soft prox)."""
-    opts = ctypes.byref(_libmod.ista_opts(algorithm=int(algorithm))) if algorithm else None
+    (n <= 64, K = 256, skimage / soft prox, accel "off").  Query it with the call's own algorithm and
+    accel: "fista" runs the row-split kernel at the resident sizes too, and the generic path then
+    keeps one more chunk of coefficients."""
+    acc = ista_accel(accel)
+    opts = ctypes.byref(_libmod.ista_opts(algorithm=int(algorithm), accel=acc)) if algorithm or acc else None
     nbytes = int(lib().lrs_ista_workspace(int(n), int(K), int(prox), opts))
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
 
 
 def ista(Yb, obs, D, n: int, alpha, thr, Nit: int, prox: int = PROX_NLM, phi=None, coefs=None,
          want_coefs=False, ws=None, stream=None, precision: int | None = None, max_workgroups: int = 0,
-         algorithm: int = 0, warm_start: bool = False):
+         algorithm: int = 0, warm_start: bool = False, accel: str = "off"):
     """Masked ISTA + prox over all blocks; returns phi (nb, n_pad) [, coefs (nb, K)].  `ws`: an
     ista_workspace() buffer (allocated here when None and needed).  precision / max_workgroups /
-    algorithm / warm_start: this call's lrs_ista_opts (None / 0 = the library defaults; algorithm 1 =
+    algorithm / warm_start / accel: this call's lrs_ista_opts (None / 0 = the library defaults; algorithm 1 =
     the generic dense-GEMM path that K > 512 always takes; warm_start: continue from `coefs`, which
-    must be given, and write the result back to it)."""
+    must be given, and write the result back to it; accel "fista": Nesterov momentum on the same
+    gradient step and prox (include/lrspnp.h), restarted by every call, so warm-started slices of an
+    accelerated run are not one call)."""
     L = device_lib()
     _dev(Yb, torch.float32, "Yb")
     _dev(obs, torch.uint8, "obs")
@@ -151,12 +156,13 @@ def ista(Yb, obs, D, n: int, alpha, thr, Nit: int, prox: int = PROX_NLM, phi=Non
         want_coefs = True
     if want_coefs and coefs is None:
         coefs = torch.empty((nb, K), dtype=torch.float32, device=Yb.device)
+    acc = ista_accel(accel)
     if ws is None:
-        ws = ista_workspace(n, K, prox, Yb.device, algorithm)
+        ws = ista_workspace(n, K, prox, Yb.device, algorithm, accel)
     opts = None
-    if precision is not None or max_workgroups or algorithm or warm_start:
+    if precision is not None or max_workgroups or algorithm or warm_start or acc:
         opts = ctypes.byref(_libmod.ista_opts(_libmod.ISTA_SPLIT_BF16 if precision is None else int(precision),
-                                              int(max_workgroups), int(algorithm), 1 if warm_start else 0))
+                                              int(max_workgroups), int(algorithm), 1 if warm_start else 0, acc))
     check(L.lrs_ista_f32(_p(Yb), _p(obs), _p(D), n, n_pad, K, nb, _p(alpha), _p(thr), int(Nit), int(prox),
                          _p(coefs) if want_coefs else None, _p(phi), opts, _p(ws), 0 if ws is None else ws.numel(),
                          _s(stream)), "lrs_ista_f32")
@@ -206,11 +212,12 @@ def ista_pat_prepare(D, obs_pat, n: int, ws=None, stream=None) -> torch.Tensor:
 
 
 def ista_pat(Yb, obs_pat, plan, ntiles: int, K: int, n: int, alpha, thr, Nit: int, ws, prox: int = PROX_NLM,
-             phi=None, coefs=None, want_coefs=False, stream=None, max_workgroups: int = 0, warm_start: bool = False):
+             phi=None, coefs=None, want_coefs=False, stream=None, max_workgroups: int = 0, warm_start: bool = False,
+             accel: str = "off"):
     """Masked ISTA + prox on per-pattern Grams (lrs_ista_pat_f32) for blocks that share observation
     patterns, on the images ista_pat_prepare() left in `ws`.  obs_pat (npat, n_pad) u8 and plan
-    (ista_pat_plan's, as an int32 device tensor) on the device; the rest as ista().  Returns
-    phi [, coefs]."""
+    (ista_pat_plan's, as an int32 device tensor) on the device; the rest as ista(), accel included.
+    Returns phi [, coefs]."""
     L = device_lib()
     _dev(Yb, torch.float32, "Yb")
     _dev(obs_pat, torch.uint8, "obs_pat")
@@ -229,8 +236,10 @@ def ista_pat(Yb, obs_pat, plan, ntiles: int, K: int, n: int, alpha, thr, Nit: in
     if want_coefs and coefs is None:
         coefs = torch.empty((nb, K), dtype=torch.float32, device=Yb.device)
     opts = None
-    if max_workgroups or warm_start:
-        opts = ctypes.byref(_libmod.ista_opts(_libmod.ISTA_SPLIT_BF16, int(max_workgroups), 0, 1 if warm_start else 0))
+    acc = ista_accel(accel)
+    if max_workgroups or warm_start or acc:
+        opts = ctypes.byref(_libmod.ista_opts(_libmod.ISTA_SPLIT_BF16, int(max_workgroups), 0, 1 if warm_start else 0,
+                                              acc))
     check(L.lrs_ista_pat_f32(_p(Yb), _p(obs_pat), npat, _p(plan), int(ntiles), n, n_pad, int(K), nb, _p(alpha),
                              _p(thr), int(Nit), int(prox), _p(coefs) if want_coefs else None, _p(phi), opts, _p(ws),
                              ws.numel(), _s(stream)), "lrs_ista_pat_f32")

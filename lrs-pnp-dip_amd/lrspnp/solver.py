@@ -75,6 +75,10 @@ class LrsPnPConfig:
     # pattern, 2 K^2 instead of 4 n K FLOP per block and iteration): "auto" when the library's cost
     # model prefers it (few patterns, n > K / 2), "on" whenever the block length allows it, "off".
     ista_patterns: str = "auto"
+    # Sparse-coding iteration: "off", the reference's ISTA, or "fista", the same gradient step and prox
+    # with Nesterov momentum (lrs_ista_opts.accel), on whichever path the solver picks.  An accelerated
+    # call restarts its momentum, so slices of one are not one call: refused with ista_slices_dip > 1.
+    ista_accel: str = "off"
     # D="learn": the lrspnp.dictlearn.DictLearnConfig of the training run (None: its defaults); bb and
     # lambda_ista are always this config's own
     dict_cfg: object = None
@@ -206,6 +210,11 @@ class LrsPnP:
             raise LrsError(f"unknown ista_dip_order {cfg.ista_dip_order!r} (beside | before)")
         if cfg.svt_multi_wg not in ("auto", "on", "off"):
             raise LrsError(f"unknown svt_multi_wg {cfg.svt_multi_wg!r} (auto | on | off)")
+        if cfg.ista_accel not in ("off", "fista"):
+            raise LrsError(f"unknown ista_accel {cfg.ista_accel!r} (off | fista)")
+        if cfg.ista_accel != "off" and int(cfg.ista_slices_dip) > 1:
+            raise LrsError("ista_accel='fista' with ista_slices_dip > 1: every accelerated call restarts its "
+                           "momentum, so the slices would not be one call")
         wide_tri, wide_mw = svt_wide_solver_flags(cfg.svt_wide_solver)
         self.svt_wide_tri, self.svt_wide_mw = self.svt_wide and wide_tri, self.svt_wide and wide_mw
         if self.K <= 512 and (cfg.ista_patterns == "on" or (
@@ -223,7 +232,7 @@ class LrsPnP:
         if self.pat_plan is not None:   # the dictionary and Gram images, once per solve (D, patterns fixed)
             self.ista_ws = ops.ista_pat_prepare(self.D, self.obs_pat, n)
         else:
-            self.ista_ws = ops.ista_workspace(n, self.K, self.prox, dev)
+            self.ista_ws = ops.ista_workspace(n, self.K, self.prox, dev, accel=cfg.ista_accel)
         self.norms = torch.zeros(3, dtype=torch.float64, device=dev)
         self.lowrank_stream = torch.cuda.Stream(device=dev, priority=int(cfg.lowrank_priority))
         self.iteration = 0
@@ -293,10 +302,10 @@ class LrsPnP:
             return ops.ista_pat(self.Yb, self.obs_pat, self.pat_plan, self.pat_ntiles, self.K, self.n, self.alpha,
                                 self.thr, Nit, self.ista_ws, self.prox, phi=self.phi, coefs=coefs,
                                 want_coefs=want_coefs, stream=stream, max_workgroups=max_workgroups,
-                                warm_start=warm_start)
+                                warm_start=warm_start, accel=self.cfg.ista_accel)
         return ops.ista(self.Yb, self.obs, self.D, self.n, self.alpha, self.thr, Nit, self.prox, phi=self.phi,
                         coefs=coefs, want_coefs=want_coefs, ws=self.ista_ws, stream=stream,
-                        max_workgroups=max_workgroups, warm_start=warm_start)
+                        max_workgroups=max_workgroups, warm_start=warm_start, accel=self.cfg.ista_accel)
 
     def sparse_coding_range(self, b0: int, b1: int, stream=None):
         """Phi rows [b0, b1) only (the blocks of one task-parallel worker, lrspnp.dist.DipTaskSplit)."""
@@ -307,10 +316,10 @@ class LrsPnP:
         ws = self.ista_ws
         if self.pat_plan is not None:   # a block range runs the row-split kernel, on a workspace of its own
             if getattr(self, "_rs_ws", None) is None:
-                self._rs_ws = ops.ista_workspace(self.n, self.K, self.prox, self.Yb.device)
+                self._rs_ws = ops.ista_workspace(self.n, self.K, self.prox, self.Yb.device, accel=self.cfg.ista_accel)
             ws = self._rs_ws
         ops.ista(self.Yb[b0:b1], self.obs[b0:b1], self.D, self.n, self.alpha[b0:b1], self.thr[b0:b1], self.cfg.Nit,
-                 self.prox, phi=self.phi[b0:b1], ws=ws, stream=stream)
+                 self.prox, phi=self.phi[b0:b1], ws=ws, stream=stream, accel=self.cfg.ista_accel)
 
     def admm(self, stream=None):
         """col2im + closed-form X + dual updates from the current Phi and U (main_LRS_PnP.py:324-366)."""
