@@ -330,6 +330,7 @@ int lrs_admm_update_f32(float *X, float *L1, float *L2, const float *Y, const fl
 #define LRS_ACT_NONE 0
 #define LRS_ACT_LRELU 1   /* LeakyReLU(0.2) */
 #define LRS_ACT_SIGMOID 2
+#define LRS_ACT_RELU 3    /* ReLU: LRS_NODE_DECODE and lrs_up2_bilinear_act_* only (LRS_E_INVALID elsewhere) */
 
 /* Output size of the conv unit (upsample, pad, k, stride). */
 int lrs_conv2d_out_size(int H, int W, int k, int stride, int pad, int upsample, int *Ho, int *Wo);
@@ -379,6 +380,18 @@ int lrs_conv_bn_small_f32(const float *x, int Cin, int H, int W, const float *w,
                           int k, int stride, int pad, int pad_mode, int upsample, const float *gamma,
                           const float *beta, int lip, int act, float *z, float *y, float *mean, float *invstd,
                           float *run_mean, float *run_var, void *stream);
+/* Bilinear x2 upsampling fused with an activation, the two kernels of a Deep Decoder stage
+ * (LRS_NODE_DECODE; include/decoder.py decodernw: nn.Upsample(scale_factor=2, mode='bilinear'), then
+ * act_fun).  x is [C][H][W], y and gy are [C][2H][2W].  align_corners=False: per axis output 2s + p takes
+ * 3/4 of source s and 1/4 of s - 1 (p = 0) or s + 1 (p = 1), that index clamped at both edges.
+ *   _fwd: y = act(up2(x)).
+ *   _bwd: gx = up2^T(gy .* act'(y)), a gather in a fixed order (no atomics: reruns are bit-identical);
+ *         act' is taken from the sign of the stored y (y = 0: the slope of x <= 0, as torch).
+ * act: LRS_ACT_NONE, LRS_ACT_LRELU or LRS_ACT_RELU (LRS_E_INVALID otherwise); C <= 65535 and
+ * 4 H W < 2^31 (LRS_E_UNSUPPORTED above). */
+int lrs_up2_bilinear_act_fwd_f32(const float *x, int C, int H, int W, int act, float *y, void *stream);
+int lrs_up2_bilinear_act_bwd_f32(const float *gy, const float *y, int C, int H, int W, int act, float *gx,
+                                 void *stream);
 
 /* sigma_max of n weight matrices W[i] (rows[i] x cols[i], min(rows, cols) <= 128; host arrays
  * of device pointers), within 1 float32 ulp of the fp64 SVD value for 5e-20 < sigma < 1e19, unless the
@@ -448,6 +461,18 @@ int lrs_es_update_f32(const float *out, int64_t N, float *ring, lrs_es_state *st
 #define LRS_NODE_CONV 0    /* [upsample x2] -> pad -> conv(k, stride) -> [BN] -> act            */
 #define LRS_NODE_BN 1      /* BN -> act on in0                                                  */
 #define LRS_NODE_CONCAT 2  /* cat(in0, [upsample x2](in1)) along channels, centre-cropped       */
+/* One Deep Decoder stage on in0 (include/decoder.py decodernw, bn_before_act=False):
+ *   conv 1x1 to cout channels, no bias -> [bilinear x2] -> act -> [BN]
+ * -- the activation comes BEFORE the BatchNorm.  Fields used: cout, upsample (0 or LRS_UP_BILINEAR), act,
+ * bn (LRS_BN_NONE or LRS_BN_PLAIN), winit.  k must be 1, stride 1, pad 0, sn 0, upsample not nearest and
+ * bn not LRS_BN_LIP: LRS_E_UNSUPPORTED from lrs_dipnet_create otherwise.  act: NONE, LRELU, RELU, or
+ * SIGMOID with upsample = 0 and bn = 0 only (the head; LRS_E_INVALID with either).  The node owns a weight
+ * [cout][cin] and, with bn, gamma and beta; it has no bias (lrs_dipnet_param_offsets: b = -1).  As the
+ * last node, a stage without upsampling and BN takes the loss head a bias-free CONV head would. */
+#define LRS_NODE_DECODE 3
+/* upsample values: 0 none, 1 nearest (CONV / CONCAT, which take any non-zero value but LRS_UP_BILINEAR as
+ * nearest and refuse LRS_UP_BILINEAR with LRS_E_INVALID), 2 bilinear (DECODE only) */
+#define LRS_UP_BILINEAR 2
 #define LRS_BN_NONE 0
 #define LRS_BN_PLAIN 1     /* nn.BatchNorm2d, train mode (models/common.py:71)                 */
 #define LRS_BN_LIP 2       /* BatchNormSpectralNorm-wrapped (lipschitz_constraint_layer.py:88)  */
@@ -501,7 +526,9 @@ int lrs_dipnet_get_frame(const lrs_dipnet *net, int *top, int *left, int *H, int
 const float *lrs_dipnet_output(const lrs_dipnet *net);
 const float *lrs_dipnet_grads(const lrs_dipnet *net);
 /* diagnostics: node i's buffers in the workspace after a forward / backward (NULL where absent):
- * its output, its pre-BatchNorm z, dL/dz, dL/d(output) */
+ * its output, its pre-BatchNorm z, dL/dz, dL/d(output).  A DECODE stage with BatchNorm: z is the
+ * activation a the BatchNorm reads (the node's shape), dL/dz its gradient; a DECODE stage without: as a
+ * CONV without BatchNorm where it neither upsamples nor applies ReLU, else NULL for both. */
 #define LRS_BUF_OUT 0
 #define LRS_BUF_Z 1
 #define LRS_BUF_GZ 2

@@ -21,6 +21,7 @@
 #include "dip_sm.h"
 #include "dip_dir.h"
 #include "dip_image.h"
+#include "dip_up.h"
 #include "ista_paths.h"
 
 using namespace lrs;
@@ -709,6 +710,60 @@ int bn_bwd(const float *gy, const float *y, const float *z, const float *gamma, 
         if (gamma || gbias) hipLaunchKernelGGL(k_bn_bwd_stats, dim3(S, C), dim3(kBnThreads), 0, st, a);
         hipLaunchKernelGGL(k_bn_bwd_apply, dim3(S, C), dim3(kBnThreads), 0, st, a);
     }
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
+// ---- the Deep Decoder stage's kernels (dip_up.h) -------------------------------------------------
+inline bool dec_act_ok(int act) { return act == LRS_ACT_NONE || act == LRS_ACT_LRELU || act == LRS_ACT_RELU; }
+
+// Block (bx, 256 / bx) over (source column pairs, source rows): bx = the width of 16, 32 or 64 that pads
+// the row of column pairs least (the wider on ties); grid z = channels.
+struct Up2Grid { dim3 grid, block; };
+inline int up2_grid(int C, int H, int W, Up2Grid &u) {
+    if (C <= 0 || H <= 0 || W <= 0) return LRS_E_INVALID;
+    if (C > 65535 || (int64_t)4 * H * W > INT32_MAX) return LRS_E_UNSUPPORTED;
+    const int wp = (W + 1) / 2;
+    int bx = 64;
+    for (int b : {32, 16})
+        if ((wp + b - 1) / b * b < (wp + bx - 1) / bx * bx) bx = b;
+    const int by = 256 / bx;
+    if ((H + by - 1) / by > 65535) return LRS_E_UNSUPPORTED;
+    u.block = dim3(bx, by);
+    u.grid = dim3((wp + bx - 1) / bx, (H + by - 1) / by, C);
+    return LRS_OK;
+}
+
+// a[C][2H][2W] = act(up2(z[C][H][W]))
+int up2_fwd(const float *z, int C, int H, int W, int act, float *a, hipStream_t st) {
+    Up2Grid u;
+    if (const int rc = up2_grid(C, H, W, u)) return rc;
+    const int vec = (W % 2 == 0 && al16(a)) ? 1 : 0;
+    hipLaunchKernelGGL(k_up2_bilinear_act, u.grid, u.block, 0, st, z, a, H, W, act, vec);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
+// gz[C][H][W] = up2^T(ga .* act'(a))
+int up2_bwd(const float *ga, const float *a, int C, int H, int W, int act, float *gz, hipStream_t st) {
+    Up2Grid u;
+    if (const int rc = up2_grid(C, H, W, u)) return rc;
+    const int vec = (W % 2 == 0 && al16(ga) && al16(a)) ? 1 : 0;
+    hipLaunchKernelGGL(k_up2_bilinear_act_bwd, u.grid, u.block, 0, st, ga, a, gz, H, W, act, vec);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+
+// the stage that does not upsample: a = act(z) / gz = ga .* act'(a) over n elements
+int dec_act_fwd_launch(const float *z, float *a, int64_t n, int act, hipStream_t st) {
+    const int vec = (al16(z) && al16(a)) ? 1 : 0;
+    hipLaunchKernelGGL(k_dec_act, dim3(ew_blocks((n + 3) / 4)), dim3(kEw), 0, st, z, a, n, act, vec);
+    LRS_CHECK_LAUNCH();
+    return LRS_OK;
+}
+int dec_act_bwd_launch(const float *ga, const float *a, float *gz, int64_t n, int act, hipStream_t st) {
+    const int vec = (al16(ga) && al16(a) && al16(gz)) ? 1 : 0;
+    hipLaunchKernelGGL(k_dec_act_bwd, dim3(ew_blocks((n + 3) / 4)), dim3(kEw), 0, st, ga, a, gz, n, act, vec);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }

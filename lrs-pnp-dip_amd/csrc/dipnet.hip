@@ -171,6 +171,18 @@ extern "C" int lrs_conv_bn_small_f32(const float *x, int Cin, int H, int W, cons
     return LRS_OK;
 }
 
+// The Deep Decoder stage's two kernels (dip_up.h) on their own
+extern "C" int lrs_up2_bilinear_act_fwd_f32(const float *x, int C, int H, int W, int act, float *y, void *stream) {
+    if (!x || !y || !dec_act_ok(act)) return LRS_E_INVALID;
+    return up2_fwd(x, C, H, W, act, y, (hipStream_t)stream);
+}
+
+extern "C" int lrs_up2_bilinear_act_bwd_f32(const float *gy, const float *y, int C, int H, int W, int act, float *gx,
+                                            void *stream) {
+    if (!gy || !y || !gx || !dec_act_ok(act)) return LRS_E_INVALID;
+    return up2_bwd(gy, y, C, H, W, act, gx, (hipStream_t)stream);
+}
+
 extern "C" size_t lrs_sigma_max_workspace(int n) {
     if (n <= 0) return 0;
     return (size_t)n * kSnGramDoubles * sizeof(double) + (size_t)n * sizeof(SnConv) + 256;
@@ -426,6 +438,29 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
                             bn ? net->bnstats + N.rs_off + N.C : nullptr, N.C, N.P, N.d.act, 1e-5f, 0.1f, net->bnpart(), st,
                             lip);
             }
+        } else if (N.d.kind == LRS_NODE_DECODE) {
+            // the bias-free 1x1 on its own map (k_pw from the planes, else the dense GEMM), then the stage's tail
+            const float *xin = net->tensor(N.d.in0, x), *w = net->params + N.w_off;
+            const __bf16 *wp = N.wpre_off >= 0 ? net->at<__bf16>(N.wpre_off) : nullptr;
+            float *part = net->f(net->part_off);
+            if (!N.dec_tail) {   // the head: a CONV without BN and without bias
+                const bool act_pw = N.plan.bn == BnFwd::ActInPw;
+                rc = conv_fwd(N.g, xin, w, nullptr, N.C, nullptr, out, part, net->part_cap, st, wp, nullptr,
+                              act_pw ? N.d.act : 0, (act_pw && i + 1 == net->nodes.size()) ? head : nullptr);
+                if (!rc && !act_pw)
+                    rc = bn_fwd(out, out, nullptr, nullptr, net->f(N.mean_off), net->f(N.istd_off), nullptr, nullptr, N.C,
+                                N.P, N.d.act, 1e-5f, 0.1f, net->bnpart(), st, 0);
+            } else {
+                float *z = net->f(N.z_off), *a = N.d.bn ? net->f(N.a_off) : out;
+                rc = conv_fwd(N.g, xin, w, nullptr, N.C, nullptr, z, part, net->part_cap, st, wp);
+                if (!rc)
+                    rc = N.d.upsample ? up2_fwd(z, N.C, N.g.Ho, N.g.Wo, N.d.act, a, st)
+                                      : dec_act_fwd_launch(z, a, (int64_t)N.C * N.P, N.d.act, st);
+                if (!rc && N.d.bn)   // the path of LRS_NODE_BN, on a
+                    rc = bn_fwd(a, out, net->params + N.gm_off, net->params + N.bt_off, net->f(N.mean_off),
+                                net->f(N.istd_off), net->bnstats + N.rs_off, net->bnstats + N.rs_off + N.C, N.C, N.P,
+                                LRS_ACT_NONE, 1e-5f, 0.1f, net->bnpart(), st, 0);
+            }
         } else if (N.d.kind == LRS_NODE_BN) {
             rc = bn_fwd(net->tensor(N.d.in0, x), out, net->params + N.gm_off, net->params + N.bt_off,
                         net->f(N.mean_off), net->f(N.istd_off), net->bnstats + N.rs_off, net->bnstats + N.rs_off + N.C,
@@ -464,11 +499,11 @@ int mse_head(lrs_dipnet *net, const float *out, const float *target, const float
     if (!net->framed)
         hipLaunchKernelGGL(k_mse_head, dim3((unsigned)S, (unsigned)N.C), dim3(256), 0, st, out, target, mask, mstride, N.C,
                            P, (int)chunk, vec, N.d.act, gz, net->loss_acc(), net->bnpart(), net->headcnt(),
-                           net->grads + N.b_off);
+                           net->head_gbias(N));
     else
         hipLaunchKernelGGL(k_mse_head_n, dim3((unsigned)S, (unsigned)N.C), dim3(256), 0, st, out, target, mask, mstride,
                            N.C, P, (int)chunk, vec, N.d.act, gz, net->loss_acc(), net->bnpart(), net->headcnt(),
-                           net->grads + N.b_off, net->n_mean());
+                           net->head_gbias(N), net->n_mean());
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
@@ -529,7 +564,7 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
         if (!head_reduce) return;
         const auto &Lh = net->nodes[n - 1];
         hipLaunchKernelGGL(k_head_reduce, dim3((unsigned)Lh.C), dim3(256), 0, hs, (const double *)net->hpart(), Lh.C,
-                           net->head_nwg, net->grads + Lh.b_off, net->closs());
+                           net->head_nwg, net->head_gbias(Lh), net->closs());
         hipLaunchKernelGGL(k_head_loss, dim3(1), dim3(64), 0, hs, (const double *)net->closs(), Lh.C, net->loss_acc());
         head_reduce = false;
     };
@@ -537,7 +572,7 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
     std::vector<char> written(n + 1, 0);
     written[n] = 1;
     int first_conv = 0;
-    while (first_conv < n && net->nodes[first_conv].d.kind != LRS_NODE_CONV) ++first_conv;
+    while (first_conv < n && !has_conv(net->nodes[first_conv])) ++first_conv;
     // conv node j's weight gradient on the side stream, forked right after its BN backward (its dL/dz is
     // complete by then).  Until round 5 a run of small maps forked every second conv (a fork cost the
     // critical stream ~7 us with system-scope events); with the device-scope events (ensure_side) forking
@@ -561,11 +596,31 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
         float *outp = net->f(N.out_off);
         const int lip = N.d.bn == 2 ? 1 : 0;
         if (!written[i + 1]) continue;   // output unused by the loss (cannot happen for a valid net)
-        if (N.d.kind == LRS_NODE_CONV) {
+        if (has_conv(N)) {
             const bool bn = N.d.bn != 0;
             float *z = bn ? net->f(N.z_off) : outp;
             float *gz = net->f(N.gz_off);
-            if (pend) {
+            if (N.d.kind == LRS_NODE_DECODE) {
+                // dL/dz on the conv's map: [BN backward (the path of LRS_NODE_BN) ->] the upsampling's
+                // adjoint with the activation's derivative; the head as a CONV without BN and bias
+                rc = LRS_OK;
+                if (N.dec_tail) {
+                    const float *ga = gout, *a = bn ? net->f(N.a_off) : outp;
+                    if (bn) {
+                        rc = bn_bwd(gout, outp, a, net->params + N.gm_off, net->f(N.mean_off), net->f(N.istd_off),
+                                    net->f(N.ga_off), net->grads + N.gm_off, net->grads + N.bt_off, nullptr, N.C, N.P,
+                                    LRS_ACT_NONE, net->bnpart(), st, 0, 0, net->params + N.bt_off);
+                        ga = net->f(N.ga_off);
+                    }
+                    if (!rc)
+                        rc = N.d.upsample ? up2_bwd(ga, a, N.C, N.g.Ho, N.g.Wo, N.d.act, gz, st)
+                                          : dec_act_bwd_launch(ga, a, gz, (int64_t)N.C * N.P, N.d.act, st);
+                } else if (!(head_done && i == n - 1)) {   // else the loss head wrote gz
+                    rc = bn_bwd(gout, outp, outp, nullptr, net->f(N.mean_off), net->f(N.istd_off), gz, nullptr, nullptr,
+                                nullptr, N.C, N.P, N.d.act, net->bnpart(), st, 0);
+                }
+                if (rc) return rc;
+            } else if (pend) {
                 launch_reduce_bn_bwd1(pend, pend_S, net->bn_bwd_args(N), st);
                 pend = nullptr;
             } else if (!(head_done && i == n - 1)) {   // else k_mse_head wrote gz and the bias gradient
@@ -860,7 +915,7 @@ extern "C" int lrs_dipnet_bind(lrs_dipnet *net, float *params, float *grads, flo
     std::vector<ConvPrep> prep;
     for (size_t i = 0; i < net->nodes.size(); ++i) {
         const auto &N = net->nodes[i];
-        if (N.d.kind != LRS_NODE_CONV || (N.sn_index < 0 && N.wpre_off < 0)) continue;
+        if (!has_conv(N) || (N.sn_index < 0 && N.wpre_off < 0)) continue;
         __bf16 *wf = N.wpre_off >= 0 ? net->at<__bf16>(N.wpre_off) : nullptr;
         __bf16 *wd = (wf && N.d.in0 > 0) ? wf + wprep_elems(N.g, N.C, N.upc).fwd : nullptr;
         prep.push_back(ConvPrep{params + N.w_off, N.sn_index >= 0 ? net->f(N.wn_off) : nullptr, wf, wd, N.C, N.g.Cin,
@@ -904,7 +959,7 @@ extern "C" int lrs_dipnet_init_params(lrs_dipnet *net, uint64_t seed, void *stre
     for (size_t i = 0; i < net->nodes.size(); ++i) {
         const auto &N = net->nodes[i];
         const uint64_t k1 = mix64(seed * 0x100000001b3ULL + 2 * i + 1), k2 = mix64(seed * 0x100000001b3ULL + 2 * i + 2);
-        if (N.d.kind == LRS_NODE_CONV) {
+        if (has_conv(N)) {
             const float fan_in = (float)N.Kc;
             // kaiming_uniform_(a=0, fan_in) (lipschitz_constraint_layer.py:74) or the nn.Conv2d
             // default kaiming_uniform_(a=sqrt(5)) = U(-1/sqrt(fan_in), +)
@@ -912,7 +967,8 @@ extern "C" int lrs_dipnet_init_params(lrs_dipnet *net, uint64_t seed, void *stre
             const float bb = 1.0f / sqrtf(fan_in);
             hipLaunchKernelGGL(k_init_uniform, dim3(ew_blocks(N.C * N.Kc)), dim3(kEw), 0, st, net->params + N.w_off,
                                (int64_t)(N.C * N.Kc), wb, k1);
-            hipLaunchKernelGGL(k_init_uniform, dim3(1), dim3(kEw), 0, st, net->params + N.b_off, (int64_t)N.C, bb, k2);
+            if (N.b_off >= 0)   // (a DECODE stage has no bias)
+                hipLaunchKernelGGL(k_init_uniform, dim3(1), dim3(kEw), 0, st, net->params + N.b_off, (int64_t)N.C, bb, k2);
         }
         if (N.d.bn) {
             hipLaunchKernelGGL(k_fill, dim3(1), dim3(kEw), 0, st, net->params + N.gm_off, (int64_t)N.C, 1.0f);
@@ -991,6 +1047,8 @@ extern "C" const float *lrs_dipnet_node_buffer(const lrs_dipnet *net, int node, 
     else if (which == LRS_BUF_Z) off = N.z_off;
     else if (which == LRS_BUF_GZ) off = N.gz_off;
     else if (which == LRS_BUF_GRAD) off = N.grad_off;
+    if (N.dec_tail && which == LRS_BUF_Z) off = N.a_off;    // what its BatchNorm reads, at the node's shape
+    if (N.dec_tail && which == LRS_BUF_GZ) off = N.ga_off;   // (z and dL/dz live on the conv's smaller map)
     return off >= 0 ? net->f(off) : nullptr;
 }
 

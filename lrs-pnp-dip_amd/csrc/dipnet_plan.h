@@ -50,6 +50,13 @@ struct lrs_dipnet {
         int64_t out_off = 0, z_off = -1, col_off = -1, mean_off = -1, istd_off = -1, wn_off = -1, grad_off = 0;
         int64_t wpre_off = -1;        // implicit convs: bf16 weight planes (wprep)
         int64_t gz_off = -1;          // conv: dL/dz (read by the side-stream weight gradient)
+        // DECODE (conv 1x1 -> [bilinear x2] -> act -> [BN]).  dec_tail: the stage runs the decoder's own
+        // kernels after the product: z (z_off, [C][h][w], the conv's map) -> a = act(up2(z)) (a_off with BN,
+        // else the output) -> BN -> output; backward ga_off = dL/da (with BN, else the output gradient),
+        // gz_off = dL/dz on the conv's map.  Without it (no upsampling, no BN, no ReLU: the head) the node
+        // runs as a bias-free CONV without BN, loss heads included; their bias-gradient sums go to gbsink_off.
+        bool dec_tail = false;
+        int64_t a_off = -1, ga_off = -1, gbsink_off = -1;
         int sn_index = -1;            // position in the spectral-norm table
         bool sm = false;              // small map: forward / data gradient on k_conv_sm (dip_sm.h)
         bool upc = false;             // upsampled 3 x 3: forward / data gradient by output parity class
@@ -132,6 +139,8 @@ struct lrs_dipnet {
     double *bnpart() const { return at<double>(bnpart_off); }
     double *hpart() const { return at<double>(hpart_off); }
     double *closs() const { return at<double>(closs_off); }
+    // where a loss head puts the last node's bias gradient (a DECODE head has no bias: a scratch row)
+    float *head_gbias(const Node &N) const { return N.b_off >= 0 ? grads + N.b_off : f(N.gbsink_off); }
     const float *tensor(int t, const float *x) const { return t == 0 ? x : f(nodes[t - 1].out_off); }
     int tC(int t) const { return t == 0 ? C0 : nodes[t - 1].C; }
     int tH(int t) const { return t == 0 ? H : nodes[t - 1].H; }
@@ -178,6 +187,11 @@ static_assert(kDirMaxP < kForkBigP && 4 * kBn1Threads < kForkBigP, "the overlapp
 // ---- the plan: the only place that names these predicates -------------------------------------
 using Node = lrs_dipnet::Node;
 
+// a node with a conv product: weights, planes, weight and data gradients
+inline bool has_conv(const Node &N) { return N.d.kind == LRS_NODE_CONV || N.d.kind == LRS_NODE_DECODE; }
+// ... whose forward follows the CONV plan (a DECODE stage with a tail runs its own chain)
+inline bool conv_planned(const Node &N) { return has_conv(N) && !N.dec_tail; }
+
 void plan_fwd(Node &N) {
     const bool on_planes = plain_unit(N.g) ? N.wpre_off >= 0 : N.col_off < 0;
     if (N.d.bn && N.sm && N.P <= kDirMaxP && dir_geom(N.g, N.plan.dg)) N.plan.fwd = Fwd::Direct;
@@ -223,7 +237,7 @@ bool plan_sn_overlap(const lrs_dipnet *net) {
 // the alignment-dependent part, once the workspace is known
 void plan_bind(lrs_dipnet *net) {
     for (Node &N : net->nodes)
-        if (N.d.kind == LRS_NODE_CONV) plan_bn_fwd(N, al16(net->ws));
+        if (conv_planned(N)) plan_bn_fwd(N, al16(net->ws));
     net->sn_overlap = plan_sn_overlap(net);
 }
 
@@ -246,7 +260,12 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
         N.d = nodes[i];
         const int t0 = N.d.in0;
         if (t0 < 0 || t0 > i) return LRS_E_INVALID;
-        if (N.d.act != LRS_ACT_NONE && N.d.act != LRS_ACT_LRELU && N.d.act != LRS_ACT_SIGMOID) return LRS_E_INVALID;
+        if (N.d.act != LRS_ACT_NONE && N.d.act != LRS_ACT_LRELU && N.d.act != LRS_ACT_SIGMOID &&
+            !(N.d.act == LRS_ACT_RELU && N.d.kind == LRS_NODE_DECODE))
+            return LRS_E_INVALID;
+        // bilinear upsampling is the DECODE stage's alone (every other kind: non-zero = nearest)
+        if (N.d.upsample == LRS_UP_BILINEAR && (N.d.kind == LRS_NODE_CONV || N.d.kind == LRS_NODE_CONCAT))
+            return LRS_E_INVALID;
         if (N.d.bn < 0 || N.d.bn > 2) return LRS_E_INVALID;
         const int ci = net->tC(t0), hi = net->tH(t0), wi = net->tW(t0);
         if (N.d.kind == LRS_NODE_CONV) {
@@ -299,6 +318,38 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
             max_dz = std::max(max_dz, N.C * N.P);
             plan_fwd(N);
             plan_grads(N);
+        } else if (N.d.kind == LRS_NODE_DECODE) {
+            if (N.d.cout <= 0) return LRS_E_INVALID;
+            if (N.d.k != 1 || N.d.stride != 1 || N.d.pad != 0 || N.d.sn != 0 || N.d.bn == LRS_BN_LIP ||
+                (N.d.upsample != 0 && N.d.upsample != LRS_UP_BILINEAR))
+                return LRS_E_UNSUPPORTED;
+            if (N.d.act == LRS_ACT_SIGMOID && (N.d.upsample || N.d.bn)) return LRS_E_INVALID;   // the head only
+            if (const int rc = make_geom(ci, hi, wi, 1, 1, 0, LRS_PAD_ZERO, 0, N.g, &o)) return rc;   // the 1x1 on its own map
+            const int up = N.d.upsample ? 2 : 1;
+            if ((int64_t)up * hi > INT32_MAX / 4 / ((int64_t)up * wi) || N.d.cout > 65535) return LRS_E_UNSUPPORTED;
+            N.C = N.d.cout; N.H = up * hi; N.W = up * wi;
+            N.P = (int64_t)N.H * N.W;
+            N.Kc = ci;
+            const int64_t Plo = (int64_t)hi * wi;
+            N.w_off = pofs; pofs += N.C * N.Kc;   // (no bias: b_off stays -1)
+            N.dec_tail = N.d.upsample || N.d.bn || N.d.act == LRS_ACT_RELU;
+            const int64_t planes = wprep_elems(N.g, N.C, false).total();
+            if (net->implicit && pw_ok(N.g, N.C) && Plo >= kImplicitMinP && planes < INT32_MAX / 3)
+                N.wpre_off = ws.planes(planes);   // on k_pw, as a CONV's 1x1
+            if (N.dec_tail) {
+                N.z_off = ws.floats(N.C * Plo);
+                if (N.d.bn) {
+                    N.a_off = ws.floats(N.C * N.P);
+                    N.ga_off = ws.floats(N.C * N.P);
+                }
+            } else {
+                N.gbsink_off = ws.floats(N.C);
+            }
+            N.gz_off = ws.floats(N.C * Plo);
+            part = std::max(part, conv_part_floats(N.g, N.C));
+            plan_fwd(N);
+            plan_grads(N);
+            N.plan.bn_bwd_fuse = false;   // its BatchNorm backward takes dL/dy as stored (no split-K partials)
         } else if (N.d.kind == LRS_NODE_BN) {
             if (!N.d.bn) N.d.bn = 1;
             N.C = ci; N.H = hi; N.W = wi;
@@ -321,13 +372,13 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
             return LRS_E_INVALID;
         }
         // BN partials: every BN and every conv (its bias gradient is reduced the same way)
-        if (N.d.bn || N.d.kind == LRS_NODE_CONV) max_bnpart = std::max(max_bnpart, bn_part_doubles(N.C, N.P));
+        if (N.d.bn || has_conv(N)) max_bnpart = std::max(max_bnpart, bn_part_doubles(N.C, N.P));
         if (N.d.bn) {
             N.gm_off = pofs; pofs += N.C;
             N.bt_off = pofs; pofs += N.C;
             N.rs_off = rofs; rofs += 2 * N.C;
         }
-        if (N.d.bn || N.d.kind == LRS_NODE_CONV) {   // without BN: unused placeholders (the kernels take them)
+        if (N.d.bn || has_conv(N)) {   // without BN: unused placeholders (the kernels take them)
             N.mean_off = ws.floats(N.C);
             N.istd_off = ws.floats(N.C);
         }
@@ -350,12 +401,12 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
     net->bnpart_off = ws.take(std::max<int64_t>(max_bnpart, 1) * (int64_t)sizeof(double));
     net->table_off = ws.take(std::max(n_sn, 1) * (int64_t)sizeof(SnConv));
     for (const Node &N : net->nodes)
-        if (N.d.kind == LRS_NODE_CONV && (N.sn_index >= 0 || N.wpre_off >= 0)) ++net->n_prep;
+        if (has_conv(N) && (N.sn_index >= 0 || N.wpre_off >= 0)) ++net->n_prep;
     const int64_t prep_bytes = std::max(net->n_prep, 1) * (int64_t)sizeof(ConvPrep);
     net->prep_off = ws.take(prep_bytes);
     net->prep_head_off = ws.take(256);   // one ConvPrep
     net->prep_side_off = ws.take(prep_bytes);
-    net->head_fusable = Lh.d.kind == LRS_NODE_CONV && Lh.d.bn == 0 && Lh.C <= 65535;
+    net->head_fusable = conv_planned(Lh) && Lh.d.bn == 0 && Lh.C <= 65535;
     net->head_pw = net->head_fusable && plain_unit(Lh.g) && Lh.wpre_off >= 0 && Lh.P <= kHeadPwMaxP;
     if (net->head_pw) {
         net->hpart_off = ws.take(2 * (int64_t)Lh.C * ((Lh.P + 63) / 64) * 8);   // [2][C][<= ceil(P / 64) workgroups]

@@ -25,8 +25,9 @@ import numpy as np
 from . import _lib
 
 PAD_ZERO, PAD_REFLECT = 0, 1
-ACT_NONE, ACT_LRELU, ACT_SIGMOID = 0, 1, 2
-NODE_CONV, NODE_BN, NODE_CONCAT = 0, 1, 2
+ACT_NONE, ACT_LRELU, ACT_SIGMOID, ACT_RELU = 0, 1, 2, 3   # ReLU: the DECODE stage only
+NODE_CONV, NODE_BN, NODE_CONCAT, NODE_DECODE = 0, 1, 2, 3
+UP_NONE, UP_NEAREST, UP_BILINEAR = 0, 1, 2                # bilinear: the DECODE stage only
 BN_NONE, BN_PLAIN, BN_LIP = 0, 1, 2
 WINIT_DEFAULT, WINIT_KAIMING = 0, 1
 
@@ -118,6 +119,44 @@ def skip_nodes(c_in: int = 128, c_out: int = 128, down=(128,) * 5, up=(128,) * 5
     top = level(0, 0)
     conv(top, c_out, 1, bn=BN_NONE, act=ACT_SIGMOID if need_sigmoid else ACT_NONE)   # :95-97
     return nodes
+
+
+def decode_node(src, cout, up=UP_BILINEAR, act=ACT_RELU, bn=BN_PLAIN, winit=WINIT_DEFAULT):
+    """One Deep Decoder stage (LRS_NODE_DECODE): bias-free conv 1x1 -> [bilinear x2] -> act -> [BN]."""
+    return DipNode(NODE_DECODE, src, 0, cout, 1, 1, 0, PAD_ZERO, up, bn, act, 0, winit)
+
+
+def deep_decoder_nodes(c_in: int, c_out: int, channels=(128, 128), act: str = "relu", need_sigmoid: bool = True,
+                       bn: bool = True) -> list[DipNode]:
+    """include/decoder.py decodernw(num_output_channels=c_out, num_channels_up=list(channels)) with its other
+    defaults (1x1 filters, bilinear upsampling, BatchNorm after the activation) as a chain of DECODE
+    nodes: len(channels) upsampling stages, one stage that does not upsample, and the head (1x1 conv to
+    c_out, Sigmoid).  No conv has a bias.  The net maps an h x w input of c_in = channels[0] channels
+    (the node list does not hold c_in: the engine takes it at creation) to 2^L h x 2^L w, L = len(channels)."""
+    channels = tuple(int(c) for c in channels)
+    if not channels or min(channels) <= 0:
+        raise ValueError(f"channels {channels!r}: at least one positive channel count")
+    if int(c_in) != channels[0]:
+        raise ValueError(f"the decoder's input has channels[0] = {channels[0]} channels, not {c_in}")
+    if act not in ("relu", "lrelu"):
+        raise ValueError(f"act {act!r}: relu | lrelu")
+    a = ACT_RELU if act == "relu" else ACT_LRELU
+    b = BN_PLAIN if bn else BN_NONE
+    widths = channels + (channels[-1], channels[-1])          # decoder.py: num_channels_up + [last, last]
+    nodes: list[DipNode] = []
+    for i in range(len(widths) - 1):
+        up = UP_BILINEAR if i != len(widths) - 2 else UP_NONE   # the last stage does not upsample
+        nodes.append(decode_node(len(nodes), widths[i + 1], up, a, b))
+    nodes.append(decode_node(len(nodes), int(c_out), UP_NONE, ACT_SIGMOID if need_sigmoid else ACT_NONE, BN_NONE))
+    return nodes
+
+
+def decoder_scale(nodes):
+    """2^L for a chain of DECODE nodes with L upsampling stages (the factor between its input and its
+    output); None for any other node list."""
+    if not nodes or any(nd.kind != NODE_DECODE for nd in nodes):
+        return None
+    return 2 ** sum(1 for nd in nodes if nd.upsample)
 
 
 # reference state_dict prefixes of each conv node of my_Lipschitz_Unet (named_parameters)
@@ -237,9 +276,9 @@ class DipNet:
         w, b, g, be = self.offsets[i]
         C = self.shapes[i][0]
         out = [None, None]
-        if nd.kind == NODE_CONV:
+        if nd.kind in (NODE_CONV, NODE_DECODE):
             cin = self.in_shape[0] if nd.in0 == 0 else self.shapes[nd.in0 - 1][0]
-            out = [flat[w:w + C * cin * nd.k * nd.k].view(C, cin, nd.k, nd.k), flat[b:b + C]]
+            out = [flat[w:w + C * cin * nd.k * nd.k].view(C, cin, nd.k, nd.k), flat[b:b + C] if b >= 0 else None]
         out += [flat[g:g + C] if g >= 0 else None, flat[be:be + C] if be >= 0 else None]
         return tuple(out)
 
@@ -407,31 +446,55 @@ class DipConfig:
     # 'auto': an image of a size the net does not reproduce is trained inside the smallest reflected
     # frame it does reproduce (frame_for); 'off': such a size is refused (the reference's behaviour)
     frame: str = "auto"
-    net: str = "unet1lip"         # 'unet1lip' (…1-LiP.py:214) or 'skip' (…pro.py:215-221)
+    net: str = "unet1lip"         # 'unet1lip' (…1-LiP.py:214), 'skip' (…pro.py:215-221) or 'decoder'
+                                  # (include/decoder.py decodernw, trained as include/fit.py does)
     early_stop: bool = True       # False: exactly num_iter steps (the timed-benchmark mode, §8d)
+    # net = 'decoder': num_channels_up, and the scale of its fixed uniform noise input (fit.py: U[0, 1) / 10)
+    decoder_channels: tuple = (128, 128)
+    decoder_input_scale: float = 0.1
+
+
+DECODER_INPUT_SEED = 0   # the decoder's noise input is drawn once per DipProx from this seed
 
 
 class DipProx:
     """get_DIP_out on the HIP engine (…1-LiP.py:208-264 with my_Lipschitz_Unet, …pro.py:211-272
     with skip()); one network object reused across outer iterations (re-initialised each call,
-    as the reference builds a fresh net per call)."""
+    as the reference builds a fresh net per call).
+
+    cfg.net = 'decoder': the Deep Decoder (include/decoder.py decodernw).  Its input is no image but a
+    fixed noise tensor (channels[0], Hf / 2^L, Wf / 2^L), uniform on [0, decoder_input_scale) (fit.py),
+    drawn once here from a seeded generator and kept across calls (decoder_input); run() ignores its
+    dip_input.  An image whose sides are no multiples of 2^L is trained inside the smallest frame that is."""
 
     def __init__(self, bands: int, H: int, W: int, cfg: DipConfig | None = None, device="cuda",
                  stream_priority: int = 0):
         self.cfg = cfg or DipConfig()
-        nodes = (skip_nodes(bands, bands) if self.cfg.net == "skip"
-                 else lipschitz_unet_nodes(bands, bands, self.cfg.hidden))
+        if self.cfg.net not in ("unet1lip", "skip", "decoder"):
+            raise ValueError(f"DipConfig.net is 'unet1lip', 'skip' or 'decoder', not {self.cfg.net!r}")
+        nodes = dip_nodes(self.cfg, bands)
+        scale = decoder_scale(nodes) or 1    # the decoder's input is 1 / 2^L of its output
         if self.cfg.frame not in ("auto", "off"):
             raise ValueError(f"DipConfig.frame is 'auto' or 'off', not {self.cfg.frame!r}")
         # the image's H x W at (top, left) of the Hf x Wf the net is built at (no frame: Hf, Wf = H, W)
         Hf, Wf, top, left = frame_for(nodes, H, W) if self.cfg.frame == "auto" else (H, W, 0, 0)
         self.H, self.W, self.Hf, self.Wf, self.top, self.left = H, W, Hf, Wf, top, left
         self.framed = (Hf, Wf) != (H, W)
-        out_hw = net_out_hw(nodes, Hf, Wf)   # (on the host, before any device work)
+        if Hf % scale or Wf % scale:
+            raise ValueError(f"the decoder needs sides that are multiples of {scale}, not {H}x{W} (frame='auto' pads)")
+        out_hw = net_out_hw(nodes, Hf // scale, Wf // scale)   # (on the host, before any device work)
         if out_hw != (Hf, Wf):
             raise ValueError(f"the DIP net maps {H}x{W} to {out_hw}; the reference "
                              "architecture needs sizes it reproduces (e.g. 36, 196 for the U-Net)")
-        self.net = DipNet(nodes, bands, Hf, Wf, device=device, stream_priority=stream_priority)
+        self.decoder_input = None
+        c_in = bands
+        if self.cfg.net == "decoder":
+            import torch
+            c_in = int(self.cfg.decoder_channels[0])
+            g = torch.Generator().manual_seed(DECODER_INPUT_SEED)
+            noise = torch.rand((c_in, Hf // scale, Wf // scale), generator=g, dtype=torch.float32)
+            self.decoder_input = (noise * float(self.cfg.decoder_input_scale)).to(device)
+        self.net = DipNet(nodes, c_in, Hf // scale, Wf // scale, device=device, stream_priority=stream_priority)
         if self.framed:
             self.net.set_frame(top, left, H, W)
         self.es = EarlyStopper(bands * H * W, self.cfg.es_size, self.cfg.patience, device=device)   # the image only
@@ -450,7 +513,7 @@ class DipProx:
         """target / input as the net takes it: (C, Hf, Wf) as it is, (C, H, W) reflected into the frame
         (a copy: callers on a hot path write the framed tensor themselves, ops.unfolded_to_frame)."""
         import torch
-        C = self.net.in_shape[0]
+        C = self.net.out_shape[0]   # (the image nets' input has the output's bands; the decoder's is not framed)
         if t.numel() == C * self.Hf * self.Wf:
             return t
         if t.numel() != C * self.H * self.W:
@@ -504,8 +567,12 @@ class DipProx:
         n_iter = cfg.num_iter if num_iter is None else num_iter
         net = self.net
         self.last_framed = None
+        if self.decoder_input is not None:
+            dip_input = self.decoder_input        # its own fixed noise (not framed); the argument is ignored
         if self.framed:
-            target, dip_input = self._framed_image(target, "target"), self._framed_image(dip_input, "dip_input")
+            target = self._framed_image(target, "target")
+            if self.decoder_input is None:
+                dip_input = self._framed_image(dip_input, "dip_input")
             mask = self._framed_mask(mask)
         net.mask_channels(mask)   # a mask of neither shape is refused before anything is enqueued
         stream_wait(net.stream, torch.cuda.current_stream())
@@ -556,6 +623,16 @@ class DipProx:
 LipschitzDip = DipProx   # the 1-Lip name used by the first callers
 
 
+def dip_nodes(cfg: DipConfig, bands: int) -> list[DipNode]:
+    """The node list of cfg.net for a cube of `bands` bands."""
+    if cfg.net == "skip":
+        return skip_nodes(bands, bands)
+    if cfg.net == "decoder":
+        ch = tuple(cfg.decoder_channels)
+        return deep_decoder_nodes(ch[0], bands, ch)
+    return lipschitz_unet_nodes(bands, bands, cfg.hidden)
+
+
 def dip_input_from_unfolded(Z, H: int, W: int):
     """(P, B) unfolded matrix (p = i + H j) -> (B, H, W) image (…1-LiP.py:404)."""
     B = Z.shape[1]
@@ -589,6 +666,7 @@ def sigma_max(weights, ln_lambda: float = 1.0):
 
 
 def out_size(H, W, k, stride, pad, up):
+    """Output size of one unit; up: 0 none, non-zero x2 (nearest, or UP_BILINEAR of a DECODE stage)."""
     ho, wo = ctypes.c_int(), ctypes.c_int()
     _check(_lib.lib().lrs_conv2d_out_size(H, W, k, stride, pad, up, ctypes.byref(ho), ctypes.byref(wo)),
            "lrs_conv2d_out_size")
@@ -605,7 +683,8 @@ def unet_size_ok(H: int, W: int) -> bool:
 
 def net_out_hw(nodes, H: int, W: int):
     """(Ho, Wo) the node list maps an H x W input to, by the engine's own host-side shape logic
-    (lrs_dipnet_create needs no device); None where it refuses the size."""
+    (lrs_dipnet_create needs no device); None where it refuses the size.  A Deep Decoder chain maps
+    h x w to 2^L h x 2^L w."""
     L = _lib.lib()
     arr = (DipNode * len(nodes))(*nodes)
     h = ctypes.c_void_p()
@@ -627,8 +706,14 @@ def frame_for(nodes, H: int, W: int):
     """(Hf, Wf, top, left): the smallest Hf >= H, Wf >= W the node list maps back to themselves, and
     where the image sits in that frame, top = (Hf - H) // 2, left = (Wf - W) // 2.  Host only.  For
     lipschitz_unet_nodes Hf = 16 ceil((H + 12) / 16) - 12.  ValueError when no size up to +32 fits, or
-    when a pad reaches the dimension it reflects (nn.ReflectionPad2d's rule: pad < size)."""
-    def fit(n):   # on a square probe: a size the net refuses along the other axis says nothing about this one
+    when a pad reaches the dimension it reflects (nn.ReflectionPad2d's rule: pad < size).
+    A Deep Decoder chain (decoder_scale) reproduces no size: its frame is the smallest with sides that are
+    multiples of 2^L, the sizes its h x w input maps to."""
+    scale = decoder_scale(nodes)
+
+    def fit(n):
+        if scale:
+            return -(-n // scale) * scale   # on a square probe: a size the net refuses along the other axis says nothing about this one
         for f in range(n, n + FRAME_SEARCH + 1):
             if net_out_hw(nodes, f, f) == (f, f):
                 return f
@@ -639,7 +724,8 @@ def frame_for(nodes, H: int, W: int):
         raise ValueError(f"image size {H}x{W}")
     Hf = fit(H)
     Wf = Hf if W == H else fit(W)
-    if net_out_hw(nodes, Hf, Wf) != (Hf, Wf):
+    s = scale or 1
+    if net_out_hw(nodes, Hf // s, Wf // s) != (Hf, Wf):
         raise ValueError(f"the DIP net does not reproduce {Hf}x{Wf}, the frame found for {H}x{W}")
     top, left = (Hf - H) // 2, (Wf - W) // 2
     for n, lo, f in ((H, top, Hf), (W, left, Wf)):
@@ -650,6 +736,6 @@ def frame_for(nodes, H: int, W: int):
 
 
 __all__ = ["DipNode", "DipNet", "EarlyStopper", "DipConfig", "DipProx", "LipschitzDip", "lipschitz_unet_nodes",
-           "lipschitz_unet_units", "skip_nodes",
+           "lipschitz_unet_units", "skip_nodes", "deep_decoder_nodes", "decode_node", "decoder_scale", "dip_nodes",
            "UNET_REF_NAMES", "dip_input_from_unfolded", "unfolded_from_image", "sigma_max", "unet_size_ok",
            "frame_for", "net_out_hw"]

@@ -28,7 +28,7 @@ from __future__ import annotations
 import torch
 
 from ._lib import LrsError
-from .dip import NODE_CONV, DipNet, lipschitz_unet_nodes, skip_nodes
+from .dip import NODE_CONV, NODE_DECODE, DipNet, deep_decoder_nodes, lipschitz_unet_nodes, skip_nodes
 
 
 class _DipFunction(torch.autograd.Function):
@@ -133,7 +133,7 @@ class DipModule(torch.nn.Module):
             self._flat.copy_(torch.as_tensor(flat, dtype=torch.float32).reshape(-1))
 
     def conv_weight_count(self) -> int:
-        return sum(1 for nd in self._nodes if nd.kind == NODE_CONV)
+        return sum(1 for nd in self._nodes if nd.kind in (NODE_CONV, NODE_DECODE))
 
 
 def my_Lipschitz_Unet(num_input_channels=128, num_output_channels=128, ln_lambda=1, pad="reflection", seed=0):
@@ -167,3 +167,43 @@ def skip(num_input_channels=2, num_output_channels=3, num_channels_down=(16, 32,
     n = len(num_channels_down)
     side = 2 ** (n + 1)          # the deepest map stays >= 2 (reflection pad 1)
     return DipModule(nodes, int(num_input_channels), nominal_hw=(side, side), seed=seed)
+
+
+_DECODER_UNSET = object()
+
+
+def decodernw(num_output_channels=3, num_channels_up=(128,) * 5, filter_size_up=1, need_sigmoid=True,
+              pad="reflection", upsample_mode="bilinear", act_fun=_DECODER_UNSET, bn_before_act=False,
+              bn_affine=True, upsample_first=True, seed=0):
+    """include/decoder.py decodernw: the Deep Decoder, a chain of bias-free 1x1 convs, each followed by
+    bilinear x2 upsampling, the activation and BatchNorm, then a 1x1 conv to the output bands and an
+    optional Sigmoid.  The input has num_channels_up[0] channels and 1 / 2^len(num_channels_up) of the
+    output's sides (none of it with upsample_mode='none').  Supported: filter_size_up=1 (every stage), any
+    pad (a 1x1 conv pads nothing), upsample_mode 'bilinear' or 'none', act_fun nn.ReLU() (the default) or
+    nn.LeakyReLU(0.2), bn_before_act=False, bn_affine=True, upsample_first=True; anything else raises
+    NotImplementedError naming the argument.  nn.Conv2d-default weights from the engine's seeded RNG."""
+    if act_fun is _DECODER_UNSET:
+        act_fun = torch.nn.ReLU()
+    sizes = filter_size_up if isinstance(filter_size_up, (list, tuple)) else [filter_size_up]
+    if any(int(k) != 1 for k in sizes):
+        raise NotImplementedError(f"lrspnp.nn.decodernw: filter_size_up={filter_size_up!r} (1 only)")
+    if upsample_mode not in ("bilinear", "none"):
+        raise NotImplementedError(f"lrspnp.nn.decodernw: upsample_mode={upsample_mode!r} ('bilinear' | 'none')")
+    if isinstance(act_fun, torch.nn.LeakyReLU) and abs(act_fun.negative_slope - 0.2) < 1e-12:
+        act = "lrelu"
+    elif isinstance(act_fun, torch.nn.ReLU):
+        act = "relu"
+    else:
+        raise NotImplementedError(f"lrspnp.nn.decodernw: act_fun={act_fun!r} (nn.ReLU() | nn.LeakyReLU(0.2))")
+    if bn_before_act:
+        raise NotImplementedError("lrspnp.nn.decodernw: bn_before_act=True (False only)")
+    if not bn_affine:
+        raise NotImplementedError("lrspnp.nn.decodernw: bn_affine=False (True only)")
+    if not upsample_first:
+        raise NotImplementedError("lrspnp.nn.decodernw: upsample_first=False (True only)")
+    channels = tuple(int(c) for c in num_channels_up)
+    nodes = deep_decoder_nodes(channels[0], int(num_output_channels), channels, act, bool(need_sigmoid), True)
+    if upsample_mode == "none":
+        for nd in nodes:
+            nd.upsample = 0
+    return DipModule(nodes, channels[0], nominal_hw=(4, 4), seed=seed)

@@ -10,10 +10,13 @@ finder placed first on sys.meta_path answers exactly these imports (SURVEY.md §
                                                                    when scikit-image is installed)
     from models.my_Lipschitz_Unet import my_Lipschitz_Unet      -> lrspnp.nn.my_Lipschitz_Unet
     from models.skip import skip                                -> lrspnp.nn.skip
+    from include.decoder import decodernw  (from include import *) -> lrspnp.nn.decodernw
+                                                                   (on the real include.decoder when the
+                                                                   reference's include package is found)
 
 Everything else (the reference's own models package for models.unet / models.resnet, utils,
-include, pytorch_ssim, the data files) resolves as it would without the shim.  The shim changes
-where these three names come from, nothing in the scripts.
+the rest of include (fit, resdecoder), pytorch_ssim, the data files) resolves as it would without
+the shim.  The shim changes where these four names come from, nothing in the scripts.
 """
 from __future__ import annotations
 
@@ -27,7 +30,10 @@ _TARGETS = {
     "skimage.restoration": ("lrspnp.compat", ["denoise_nl_means"]),
     "models.my_Lipschitz_Unet": ("lrspnp.nn", ["my_Lipschitz_Unet"]),
     "models.skip": ("lrspnp.nn", ["skip"]),
+    "include.decoder": ("lrspnp.nn", ["decodernw"]),
 }
+# targets that keep their real module when it is found: only the listed names are replaced on it
+_OVERRIDE_REAL = ("skimage.restoration", "include.decoder")
 # Only skimage.restoration.denoise_nl_means is replaced: when scikit-image is installed, the real
 # skimage.restoration loads and that one name is overridden on it (estimate_sigma,
 # denoise_tv_chambolle, skimage.metrics, skimage.io ... stay the real ones); without it, an empty
@@ -90,7 +96,7 @@ class _Finder(importlib.abc.MetaPathFinder):
             return importlib.util.spec_from_loader(fullname, _Loader(fullname), is_package=True)
         if fullname not in _TARGETS:
             return None
-        real = _real_spec(fullname, path) if fullname == "skimage.restoration" else None
+        real = _real_spec(fullname, path) if fullname in _OVERRIDE_REAL else None
         if real is not None and real.loader is not None:
             real.loader = _OverrideLoader(real.loader, fullname)
             return real
@@ -110,7 +116,7 @@ def install() -> None:
         mod = sys.modules.get(name)
         if mod is None or hasattr(mod, "__lrspnp_shim__"):
             continue
-        if name == "skimage.restoration":
+        if name in _OVERRIDE_REAL:
             _override(mod, name)
         else:
             del sys.modules[name]

@@ -105,6 +105,20 @@ class LrsPnPConfig:
         base.update(kw)
         return LrsPnPConfig(**base)
 
+    @staticmethod
+    def dip_decoder(**kw) -> "LrsPnPConfig":
+        """As dip_1lip, with the Deep Decoder (include/decoder.py decodernw) as the DIP prox, trained as
+        include/fit.py trains it: Adam at learning rate 0.01 for a fixed number of steps (the net is
+        under-parameterised: no stopping rule), from a fixed noise input."""
+        from .dip import DipConfig
+        dip = kw.pop("dip", None) or DipConfig(net="decoder", learning_rate=0.01, early_stop=False)
+        if dip.net != "decoder":
+            raise LrsError("dip_decoder uses the decoder network")
+        base = dict(gamma=0.5, mu1=0.1, mu2=0.1, lambda_ista=0.1, Nit=100, bb=36, sliding=36, variant="fro4",
+                    lowrank="dip", dip=dip)
+        base.update(kw)
+        return LrsPnPConfig(**base)
+
 
 _ALPHA = {"spec2": ops.ALPHA_SPEC2, "fro4": ops.ALPHA_FRO4, "soft": ops.ALPHA_SOFT, "matlab": ops.ALPHA_SPEC2}
 _PROX = {"spec2": ops.PROX_NLM, "fro4": ops.PROX_NLM, "soft": ops.PROX_SOFT, "matlab": ops.PROX_NLM_MATLAB}
@@ -250,7 +264,7 @@ class LrsPnP:
     def _init_dip(self, image_shape, dev, engine=True):
         """DIP target = the observed cube as an image, mask_bkg = the pixel mask
         (…1-LiP.py:275-301); the network is re-initialised every outer iteration (:214)."""
-        from .dip import DipConfig, LipschitzDip, frame_for, lipschitz_unet_nodes, skip_nodes
+        from .dip import DipConfig, LipschitzDip, dip_nodes, frame_for
         if image_shape is None:
             raise LrsError("lowrank='dip' needs image_shape=(H, W) with H*W = P")
         H, W = (int(v) for v in image_shape)
@@ -267,8 +281,7 @@ class LrsPnP:
         if self.dip is not None:
             self.frame = (self.dip.Hf, self.dip.Wf, self.dip.top, self.dip.left)
         elif dcfg.frame == "auto":
-            self.frame = frame_for(skip_nodes(self.B, self.B) if dcfg.net == "skip"
-                                   else lipschitz_unet_nodes(self.B, self.B, dcfg.hidden), H, W)
+            self.frame = frame_for(dip_nodes(dcfg, self.B), H, W)
         else:
             self.frame = (H, W, 0, 0)
         Hf, Wf, top, left = self.frame
@@ -286,7 +299,8 @@ class LrsPnP:
             self.dip_mask = pix.reshape(-1).contiguous()
         else:
             self.dip_mask = ops.unfolded_to_image(self.M, None, 1.0, H, W)             # (B, H, W)
-        self.dip_in = torch.empty_like(self.dip_target)
+        # (the decoder's input is its own fixed noise, DipProx.decoder_input: no image is written for it)
+        self.dip_in = None if dcfg.net == "decoder" else torch.empty_like(self.dip_target)
         self.dip_steps = []
 
     # -----------------------------------------------------------------------------------------
@@ -337,7 +351,9 @@ class LrsPnP:
     def low_rank_dip(self, stream):
         """U = DIP(X + L2/mu2) (…1-LiP.py:399-411) on `stream`; the host polls early stopping."""
         Hf, Wf, top, left = self.frame
-        if self.framed:
+        if self.dip_in is None:
+            pass
+        elif self.framed:
             ops.unfolded_to_frame(self.X, self.L2, self.c2, self.H, self.W, top, left, Hf, Wf, self.dip_in,
                                   stream=stream)
         else:

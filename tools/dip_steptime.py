@@ -4,6 +4,7 @@
 
     python tools/dip_steptime.py [--hw 196] [--bands 198] [--steps 100] [--rounds 7] [--graph]
     python tools/dip_steptime.py --hw 212 --frame 200     # a 200x200 image inside the 212x212 frame
+    python tools/dip_steptime.py --net decoder --hw 196 --bands 198 --channels 128 128   # the Deep Decoder
 """
 import argparse
 import os
@@ -12,7 +13,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "lrs-pnp-dip_amd"))
 import torch  # noqa: E402
-from lrspnp.dip import DipNet, lipschitz_unet_nodes, skip_nodes  # noqa: E402
+from lrspnp.dip import DipNet, deep_decoder_nodes, lipschitz_unet_nodes, skip_nodes  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--hw", type=int, default=196)
@@ -20,8 +21,10 @@ ap.add_argument("--bands", type=int, default=198)
 ap.add_argument("--steps", type=int, default=100)
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--graph", action="store_true")
-ap.add_argument("--net", default="unet", choices=["unet", "skip"], help="the 1-Lip U-Net (configs[2]) or the skip "
-                                                                          "net (configs[3])")
+ap.add_argument("--net", default="unet", choices=["unet", "skip", "decoder"],
+                help="the 1-Lip U-Net (configs[2]), the skip net (configs[3]) or the Deep Decoder (its fixed noise "
+                     "input is hw / 2^len(channels) on a side: hw must be a multiple of that factor)")
+ap.add_argument("--channels", type=int, nargs="+", default=[128, 128], help="--net decoder: num_channels_up")
 ap.add_argument("--priority", type=int, default=0, help="the net's stream priority (DipNet stream_priority; "
                                                          "its weight-gradient side stream follows it)")
 ap.add_argument("--es", action="store_true", help="with the device early-stopping update every step (ring 30, "
@@ -34,11 +37,19 @@ ap.add_argument("--frame", type=int, default=0, help="the side of an image centr
                                                      "(lrs_dipnet_set_frame: the loss and the early stopping on "
                                                      "the image alone, the mask 0 on the frame); 0: no frame")
 a = ap.parse_args()
-nodes = lipschitz_unet_nodes(a.bands, a.bands, 128) if a.net == "unet" else skip_nodes(a.bands, a.bands)
-net = DipNet(nodes, a.bands, a.hw, a.hw, stream_priority=a.priority)
-net.init_params(0)
 g = torch.Generator(device="cuda").manual_seed(0)
-x = torch.rand(a.bands, a.hw, a.hw, device="cuda", generator=g)
+if a.net == "decoder":
+    scale = 2 ** len(a.channels)
+    if a.hw % scale:
+        ap.error(f"--net decoder: --hw must be a multiple of {scale}")
+    nodes = deep_decoder_nodes(a.channels[0], a.bands, tuple(a.channels))
+    net = DipNet(nodes, a.channels[0], a.hw // scale, a.hw // scale, stream_priority=a.priority)
+    x = torch.rand(a.channels[0], a.hw // scale, a.hw // scale, device="cuda", generator=g) * 0.1
+else:
+    nodes = lipschitz_unet_nodes(a.bands, a.bands, 128) if a.net == "unet" else skip_nodes(a.bands, a.bands)
+    net = DipNet(nodes, a.bands, a.hw, a.hw, stream_priority=a.priority)
+    x = torch.rand(a.bands, a.hw, a.hw, device="cuda", generator=g)
+net.init_params(0)
 t = torch.rand(a.bands, a.hw, a.hw, device="cuda", generator=g)
 m = (torch.rand(a.hw, a.hw, device="cuda", generator=g) > 0.2).float()
 if a.bandmask:
