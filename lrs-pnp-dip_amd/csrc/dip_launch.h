@@ -30,6 +30,8 @@ namespace {
 
 constexpr int kEw = 256;   // elementwise block size
 constexpr int64_t kForkBigP = 9604;   // sigma beside the first conv: only where that conv's map is >= 98^2
+// every BatchNorm of the engine: nn.BatchNorm2d's defaults
+constexpr float kBnEps = 1e-5f, kBnMomentum = 0.1f;
 
 inline unsigned ew_blocks(int64_t n, int64_t cap = 4096) {
     int64_t b = (n + kEw - 1) / kEw;

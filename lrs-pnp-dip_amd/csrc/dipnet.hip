@@ -6,6 +6,9 @@
 // step in a hipGraph and replay it: the Adam step count and the early-stopping state live in
 // device memory, so a replayed step is exactly the eager step.
 // dip_launch.h: geometry and the kernel launchers; dipnet_plan.h: the net, its layout and plan.
+// Every node with a conv product (CONV, and the Deep Decoder's DECODE) runs one path: product -> the
+// stage tail the plan names (DECODE: [bilinear x2 +] activation) -> BatchNorm; a node's generic
+// BatchNorm call is lrs_dipnet::node_bn_fwd / node_bn_bwd, a bias that may be absent bias_in.
 #include "dipnet_plan.h"
 
 // Dense fp32-accurate GEMM for the library's other components (the K > 512 ISTA path,
@@ -165,7 +168,7 @@ extern "C" int lrs_conv_bn_small_f32(const float *x, int Cin, int H, int W, cons
     DirGeom dg;
     if (!dir_geom(g, dg)) return LRS_E_UNSUPPORTED;
     const int P = g.Ho * g.Wo;
-    const BnArgs a{z, y, gamma, beta, mean, invstd, run_mean, run_var, nullptr, Cout, P, 1, P, 1, act, 1e-5f, 0.1f, lip, 0};
+    const BnArgs a{z, y, gamma, beta, mean, invstd, run_mean, run_var, nullptr, Cout, P, 1, P, 1, act, kBnEps, kBnMomentum, lip, 0};
     dir_launch(g, dg, x, w, bias, a, (hipStream_t)stream);
     LRS_CHECK_LAUNCH();
     return LRS_OK;
@@ -384,17 +387,16 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
     for (size_t i = 0; i < net->nodes.size(); ++i) {
         auto &N = net->nodes[i];
         float *out = net->f(N.out_off);
-        const int lip = N.d.bn == 2 ? 1 : 0;
         if (!prep_waited && i > 0) {   // every later node may read the side stream's planes / W / scale
             const hipError_t e = hipStreamWaitEvent(st, net->ev_prep, 0);
             if (e != hipSuccess) return (int)e;
             prep_waited = true;
         }
-        if (N.d.kind == LRS_NODE_CONV) {
+        if (has_conv(N)) {
             const NodePlan &pl = N.plan;
-            const bool bn = N.d.bn != 0;
-            float *z = bn ? net->f(N.z_off) : out, *part = net->f(net->part_off);
-            const float *xin = net->tensor(N.d.in0, x), *w = net->conv_w(N).w, *bias = net->params + N.b_off;
+            // z: the product (the output itself where neither a BatchNorm nor a stage tail reads it)
+            float *z = N.z_off >= 0 ? net->f(N.z_off) : out, *part = net->f(net->part_off);
+            const float *xin = net->tensor(N.d.in0, x), *w = net->conv_w(N).w, *bias = net->bias_in(net->params, N);
             const __bf16 *wp = N.wpre_off >= 0 ? net->at<__bf16>(N.wpre_off) : nullptr;
             // these BatchNorm kernels finish the product's split-K sum themselves
             int nsplit = 1;
@@ -419,6 +421,17 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
             }
             }
             if (rc) return rc;
+            // the DECODE stage's tail: a = act([bilinear x2] z); its BatchNorm, if any, has no activation left
+            const float *bn_in = z;
+            int bn_act = N.d.act;
+            if (pl.tail != Tail::None) {
+                float *a = pl.tail_bn ? net->f(N.a_off) : out;
+                rc = pl.tail == Tail::Up2Act ? up2_fwd(z, N.C, N.g.Ho, N.g.Wo, N.d.act, a, st)
+                                             : dec_act_fwd_launch(z, a, (int64_t)N.C * N.P, N.d.act, st);
+                if (rc) return rc;
+                bn_in = a;
+                bn_act = LRS_ACT_NONE;
+            }
             // the raw-weight first conv (its product left >= 2 partials: plan_sn_overlap): its BatchNorm
             // kernel divides by the scale
             const float *sdiv = nullptr;
@@ -433,38 +446,10 @@ int dipnet_forward(lrs_dipnet *net, const float *x, hipStream_t st, bool step_be
             } else if (pl.bn == BnFwd::Reduce1 && nsplit > 1) {
                 launch_reduce_bn1(pp, nsplit, bias, net->bn_args(N, 0), sdiv, st);
             } else if (pl.bn == BnFwd::Reduce1 || pl.bn == BnFwd::Generic) {
-                rc = bn_fwd(z, out, bn ? net->params + N.gm_off : nullptr, bn ? net->params + N.bt_off : nullptr,
-                            net->f(N.mean_off), net->f(N.istd_off), bn ? net->bnstats + N.rs_off : nullptr,
-                            bn ? net->bnstats + N.rs_off + N.C : nullptr, N.C, N.P, N.d.act, 1e-5f, 0.1f, net->bnpart(), st,
-                            lip);
-            }
-        } else if (N.d.kind == LRS_NODE_DECODE) {
-            // the bias-free 1x1 on its own map (k_pw from the planes, else the dense GEMM), then the stage's tail
-            const float *xin = net->tensor(N.d.in0, x), *w = net->params + N.w_off;
-            const __bf16 *wp = N.wpre_off >= 0 ? net->at<__bf16>(N.wpre_off) : nullptr;
-            float *part = net->f(net->part_off);
-            if (!N.dec_tail) {   // the head: a CONV without BN and without bias
-                const bool act_pw = N.plan.bn == BnFwd::ActInPw;
-                rc = conv_fwd(N.g, xin, w, nullptr, N.C, nullptr, out, part, net->part_cap, st, wp, nullptr,
-                              act_pw ? N.d.act : 0, (act_pw && i + 1 == net->nodes.size()) ? head : nullptr);
-                if (!rc && !act_pw)
-                    rc = bn_fwd(out, out, nullptr, nullptr, net->f(N.mean_off), net->f(N.istd_off), nullptr, nullptr, N.C,
-                                N.P, N.d.act, 1e-5f, 0.1f, net->bnpart(), st, 0);
-            } else {
-                float *z = net->f(N.z_off), *a = N.d.bn ? net->f(N.a_off) : out;
-                rc = conv_fwd(N.g, xin, w, nullptr, N.C, nullptr, z, part, net->part_cap, st, wp);
-                if (!rc)
-                    rc = N.d.upsample ? up2_fwd(z, N.C, N.g.Ho, N.g.Wo, N.d.act, a, st)
-                                      : dec_act_fwd_launch(z, a, (int64_t)N.C * N.P, N.d.act, st);
-                if (!rc && N.d.bn)   // the path of LRS_NODE_BN, on a
-                    rc = bn_fwd(a, out, net->params + N.gm_off, net->params + N.bt_off, net->f(N.mean_off),
-                                net->f(N.istd_off), net->bnstats + N.rs_off, net->bnstats + N.rs_off + N.C, N.C, N.P,
-                                LRS_ACT_NONE, 1e-5f, 0.1f, net->bnpart(), st, 0);
+                rc = net->node_bn_fwd(N, bn_in, bn_act, st);
             }
         } else if (N.d.kind == LRS_NODE_BN) {
-            rc = bn_fwd(net->tensor(N.d.in0, x), out, net->params + N.gm_off, net->params + N.bt_off,
-                        net->f(N.mean_off), net->f(N.istd_off), net->bnstats + N.rs_off, net->bnstats + N.rs_off + N.C,
-                        N.C, N.P, N.d.act, 1e-5f, 0.1f, net->bnpart(), st, lip);
+            rc = net->node_bn_fwd(N, net->tensor(N.d.in0, x), N.d.act, st);
         } else {
             const int q = N.cg.H * ((N.cg.W + 3) / 4);
             if (N.cg.Ca + N.cg.Cb > 65535 || !al16(out)) return LRS_E_UNSUPPORTED;
@@ -593,41 +578,28 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
     for (int i = n - 1; i >= 0; --i) {
         auto &N = net->nodes[i];
         float *gout = net->f(N.grad_off);
-        float *outp = net->f(N.out_off);
-        const int lip = N.d.bn == 2 ? 1 : 0;
         if (!written[i + 1]) continue;   // output unused by the loss (cannot happen for a valid net)
         if (has_conv(N)) {
-            const bool bn = N.d.bn != 0;
-            float *z = bn ? net->f(N.z_off) : outp;
+            const NodePlan &pl = N.plan;
+            const float *outp = net->f(N.out_off);
             float *gz = net->f(N.gz_off);
-            if (N.d.kind == LRS_NODE_DECODE) {
-                // dL/dz on the conv's map: [BN backward (the path of LRS_NODE_BN) ->] the upsampling's
-                // adjoint with the activation's derivative; the head as a CONV without BN and bias
-                rc = LRS_OK;
-                if (N.dec_tail) {
-                    const float *ga = gout, *a = bn ? net->f(N.a_off) : outp;
-                    if (bn) {
-                        rc = bn_bwd(gout, outp, a, net->params + N.gm_off, net->f(N.mean_off), net->f(N.istd_off),
-                                    net->f(N.ga_off), net->grads + N.gm_off, net->grads + N.bt_off, nullptr, N.C, N.P,
-                                    LRS_ACT_NONE, net->bnpart(), st, 0, 0, net->params + N.bt_off);
-                        ga = net->f(N.ga_off);
-                    }
-                    if (!rc)
-                        rc = N.d.upsample ? up2_bwd(ga, a, N.C, N.g.Ho, N.g.Wo, N.d.act, gz, st)
-                                          : dec_act_bwd_launch(ga, a, gz, (int64_t)N.C * N.P, N.d.act, st);
-                } else if (!(head_done && i == n - 1)) {   // else the loss head wrote gz
-                    rc = bn_bwd(gout, outp, outp, nullptr, net->f(N.mean_off), net->f(N.istd_off), gz, nullptr, nullptr,
-                                nullptr, N.C, N.P, N.d.act, net->bnpart(), st, 0);
+            if (pl.tail != Tail::None) {
+                // dL/dz on the conv's map: [BatchNorm backward on a ->] the tail's adjoint with the
+                // activation's derivative
+                const float *ga = gout, *a = outp;
+                if (pl.tail_bn) {
+                    a = net->f(N.a_off);
+                    if ((rc = net->node_bn_bwd(N, a, LRS_ACT_NONE, net->f(N.ga_off), 0, st))) return rc;
+                    ga = net->f(N.ga_off);
                 }
+                rc = pl.tail == Tail::Up2Act ? up2_bwd(ga, a, N.C, N.g.Ho, N.g.Wo, N.d.act, gz, st)
+                                             : dec_act_bwd_launch(ga, a, gz, (int64_t)N.C * N.P, N.d.act, st);
                 if (rc) return rc;
             } else if (pend) {
                 launch_reduce_bn_bwd1(pend, pend_S, net->bn_bwd_args(N), st);
                 pend = nullptr;
-            } else if (!(head_done && i == n - 1)) {   // else k_mse_head wrote gz and the bias gradient
-                rc = bn_bwd(gout, outp, z, bn ? net->params + N.gm_off : nullptr, net->f(N.mean_off),
-                            net->f(N.istd_off), gz, bn ? net->grads + N.gm_off : nullptr,
-                            bn ? net->grads + N.bt_off : nullptr, net->grads + N.b_off, N.C, N.P, N.d.act,
-                            net->bnpart(), st, lip, 0, bn ? net->params + N.bt_off : nullptr);
+            } else if (!(head_done && i == n - 1)) {   // else the loss head wrote gz and the bias gradient
+                rc = net->node_bn_bwd(N, N.z_off >= 0 ? net->f(N.z_off) : outp, N.d.act, gz, 0, st);
                 if (rc) return rc;
             }
             const int t = N.d.in0;
@@ -679,18 +651,10 @@ int dipnet_backward(lrs_dipnet *net, const float *x, hipStream_t st, bool head_d
             if (t > 0) written[t] = 1;
         } else if (N.d.kind == LRS_NODE_BN) {
             const int t = N.d.in0;
-            if (t > 0) {
-                rc = bn_bwd(gout, outp, net->tensor(t, x), net->params + N.gm_off, net->f(N.mean_off),
-                            net->f(N.istd_off), net->f(net->nodes[t - 1].grad_off), net->grads + N.gm_off,
-                            net->grads + N.bt_off, nullptr, N.C, N.P, N.d.act, net->bnpart(), st, lip, written[t],
-                            net->params + N.bt_off);
-                written[t] = 1;
-            } else {   // BN straight on the input: parameter grads only
-                rc = bn_bwd(gout, outp, net->tensor(t, x), net->params + N.gm_off, net->f(N.mean_off),
-                            net->f(N.istd_off), net->f(net->dz_off), net->grads + N.gm_off, net->grads + N.bt_off,
-                            nullptr, N.C, N.P, N.d.act, net->bnpart(), st, lip, 0, net->params + N.bt_off);
-            }
-            if (rc) return rc;
+            // (BN straight on the input: parameter grads only, dL/dx into the scratch dz)
+            float *gx = t > 0 ? net->f(net->nodes[t - 1].grad_off) : net->f(net->dz_off);
+            if ((rc = net->node_bn_bwd(N, net->tensor(t, x), N.d.act, gx, t > 0 ? written[t] : 0, st))) return rc;
+            if (t > 0) written[t] = 1;
         } else {
             const int ta = N.d.in0, tb = N.d.in1;
             float *ga = ta > 0 ? net->f(net->nodes[ta - 1].grad_off) : nullptr;
@@ -967,8 +931,8 @@ extern "C" int lrs_dipnet_init_params(lrs_dipnet *net, uint64_t seed, void *stre
             const float bb = 1.0f / sqrtf(fan_in);
             hipLaunchKernelGGL(k_init_uniform, dim3(ew_blocks(N.C * N.Kc)), dim3(kEw), 0, st, net->params + N.w_off,
                                (int64_t)(N.C * N.Kc), wb, k1);
-            if (N.b_off >= 0)   // (a DECODE stage has no bias)
-                hipLaunchKernelGGL(k_init_uniform, dim3(1), dim3(kEw), 0, st, net->params + N.b_off, (int64_t)N.C, bb, k2);
+            if (float *b = net->bias_in(net->params, N))   // (a DECODE stage has no bias)
+                hipLaunchKernelGGL(k_init_uniform, dim3(1), dim3(kEw), 0, st, b, (int64_t)N.C, bb, k2);
         }
         if (N.d.bn) {
             hipLaunchKernelGGL(k_fill, dim3(1), dim3(kEw), 0, st, net->params + N.gm_off, (int64_t)N.C, 1.0f);
@@ -1047,8 +1011,9 @@ extern "C" const float *lrs_dipnet_node_buffer(const lrs_dipnet *net, int node, 
     else if (which == LRS_BUF_Z) off = N.z_off;
     else if (which == LRS_BUF_GZ) off = N.gz_off;
     else if (which == LRS_BUF_GRAD) off = N.grad_off;
-    if (N.dec_tail && which == LRS_BUF_Z) off = N.a_off;    // what its BatchNorm reads, at the node's shape
-    if (N.dec_tail && which == LRS_BUF_GZ) off = N.ga_off;   // (z and dL/dz live on the conv's smaller map)
+    const bool tail = N.plan.tail != Tail::None;
+    if (tail && which == LRS_BUF_Z) off = N.a_off;     // what its BatchNorm reads, at the node's shape
+    if (tail && which == LRS_BUF_GZ) off = N.ga_off;   // (z and dL/dz live on the conv's smaller map)
     return off >= 0 ? net->f(off) : nullptr;
 }
 

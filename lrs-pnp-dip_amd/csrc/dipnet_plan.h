@@ -1,8 +1,10 @@
 // DIP network engine: the net (struct lrs_dipnet), its workspace layout and the per-node plan: which
-// kernels serve a conv's forward product, its BatchNorm and its two gradients.  Decided once: what the
-// shape fixes by dipnet_layout (lrs_dipnet_create), what the bound workspace's alignment fixes by
-// plan_bind (lrs_dipnet_bind).  dipnet_forward, weight_grad and dipnet_backward (dipnet.hip) switch on
-// it and evaluate no predicate of their own.  Part of dipnet.hip's translation unit.
+// kernels serve a conv product's forward (a CONV's, or a DECODE stage's bias-free 1x1), the stage tail
+// after it, its BatchNorm and its two gradients.  Decided once: what the shape fixes by dipnet_layout
+// (lrs_dipnet_create), what the bound workspace's alignment fixes by plan_bind (lrs_dipnet_bind).
+// dipnet_forward, weight_grad and dipnet_backward (dipnet.hip) switch on it and evaluate no predicate of
+// their own: they ask a node's kind only to tell conv products (has_conv) from BN and CONCAT nodes.
+// Part of dipnet.hip's translation unit.
 #pragma once
 #include "dip_launch.h"
 
@@ -19,13 +21,21 @@ enum class BnFwd {    // BatchNorm + activation after the product
     Reduce1,          // k_reduce_bn1 where the product left split-K partials, else as Generic
     Generic,          // bn_fwd (the activation alone for a conv without BatchNorm)
     ActInPw,          // a 1x1 without BatchNorm: the activation in k_pw's epilogue
+    None,             // a stage tail without BatchNorm wrote the output
+};
+enum class Tail {     // a DECODE stage's step between the product z and its BatchNorm (plan_tail)
+    None,             // a CONV; the decoder head (no upsampling, no BatchNorm, no ReLU): a bias-free CONV
+    Up2Act,           // a = act(bilinear x2 of z) (up2_fwd / up2_bwd)
+    Act,              // a = act(z) (dec_act_fwd_launch / dec_act_bwd_launch)
 };
 enum class Dgrad { None, Upc, Adjoint, Gemm };   // none (reads the input) / upc_dgrad / SmAdj gather / conv_dgrad
 enum class Wgrad { Table, Im2colGemm, Upc, Gemm };   // SmWgrad gather table / k_im2col + GEMM / upc_wgrad / conv_wgrad
 
-struct NodePlan {   // of a conv node
+struct NodePlan {   // of a node with a conv product (CONV, DECODE)
     Fwd fwd = Fwd::Col;
     DirGeom dg{};
+    Tail tail = Tail::None;
+    bool tail_bn = false;        // a BatchNorm without activation on the tail's output a (else a is the output)
     BnFwd bn = BnFwd::Generic;   // plan_bind
     int nq = 0;                  // plan_bind: BnFwd::Reg's float4 quads per thread
     Dgrad dgrad = Dgrad::None;
@@ -43,19 +53,18 @@ struct lrs_dipnet {
         int C, H, W;                  // output shape
         ConvGeom g{};                 // CONV
         CatGeom cg{};                 // CONCAT
-        NodePlan plan;                // CONV
+        NodePlan plan;                // CONV, DECODE
         int64_t P = 0, Kc = 0;
         int64_t w_off = -1, b_off = -1, gm_off = -1, bt_off = -1, rs_off = -1;   // params / bn running stats (floats)
         // workspace buffers (byte offsets, -1: none)
         int64_t out_off = 0, z_off = -1, col_off = -1, mean_off = -1, istd_off = -1, wn_off = -1, grad_off = 0;
         int64_t wpre_off = -1;        // implicit convs: bf16 weight planes (wprep)
         int64_t gz_off = -1;          // conv: dL/dz (read by the side-stream weight gradient)
-        // DECODE (conv 1x1 -> [bilinear x2] -> act -> [BN]).  dec_tail: the stage runs the decoder's own
-        // kernels after the product: z (z_off, [C][h][w], the conv's map) -> a = act(up2(z)) (a_off with BN,
-        // else the output) -> BN -> output; backward ga_off = dL/da (with BN, else the output gradient),
-        // gz_off = dL/dz on the conv's map.  Without it (no upsampling, no BN, no ReLU: the head) the node
-        // runs as a bias-free CONV without BN, loss heads included; their bias-gradient sums go to gbsink_off.
-        bool dec_tail = false;
+        // DECODE (conv 1x1 -> [bilinear x2] -> act -> [BN]) with a tail (plan.tail): z (z_off, [C][h][w], the
+        // conv's map) -> a = act(up2(z)) (a_off with BN, else the output) -> BN -> output; backward ga_off =
+        // dL/da (with BN, else the output gradient), gz_off = dL/dz on the conv's map.  Without a tail (the
+        // head) the node is a CONV without bias and BN, loss heads included; their bias-gradient sums go to
+        // gbsink_off.
         int64_t a_off = -1, ga_off = -1, gbsink_off = -1;
         int sn_index = -1;            // position in the spectral-norm table
         bool sm = false;              // small map: forward / data gradient on k_conv_sm (dip_sm.h)
@@ -139,6 +148,8 @@ struct lrs_dipnet {
     double *bnpart() const { return at<double>(bnpart_off); }
     double *hpart() const { return at<double>(hpart_off); }
     double *closs() const { return at<double>(closs_off); }
+    // a node's bias in params, or its gradient in grads (base); NULL where it has none (DECODE, BN)
+    float *bias_in(float *base, const Node &N) const { return N.b_off >= 0 ? base + N.b_off : nullptr; }
     // where a loss head puts the last node's bias gradient (a DECODE head has no bias: a scratch row)
     float *head_gbias(const Node &N) const { return N.b_off >= 0 ? grads + N.b_off : f(N.gbsink_off); }
     const float *tensor(int t, const float *x) const { return t == 0 ? x : f(nodes[t - 1].out_off); }
@@ -150,14 +161,30 @@ struct lrs_dipnet {
     // the one-workgroup-per-channel BatchNorm forward kernels (vec: their float4 form)
     BnArgs bn_args(const Node &N, int vec) const {
         return {f(N.z_off), f(N.out_off), params + N.gm_off, params + N.bt_off, f(N.mean_off), f(N.istd_off),
-                bnstats + N.rs_off, bnstats + N.rs_off + N.C, nullptr, N.C, (int)N.P, 1, (int)N.P, 1, N.d.act, 1e-5f,
-                0.1f, N.d.bn == 2 ? 1 : 0, vec};
+                bnstats + N.rs_off, bnstats + N.rs_off + N.C, nullptr, N.C, (int)N.P, 1, (int)N.P, 1, N.d.act, kBnEps,
+                kBnMomentum, N.d.bn == 2 ? 1 : 0, vec};
     }
     // k_reduce_bn_bwd1: dL/dy arrives as split-K partials
     BnBwdArgs bn_bwd_args(const Node &N) const {
         return {nullptr, f(N.out_off), f(N.z_off), params + N.gm_off, f(N.mean_off), f(N.istd_off), f(N.gz_off),
-                grads + N.gm_off, grads + N.bt_off, grads + N.b_off, nullptr, N.C, (int)N.P, 1, (int)N.P, 1, N.d.act,
+                grads + N.gm_off, grads + N.bt_off, bias_in(grads, N), nullptr, N.C, (int)N.P, 1, (int)N.P, 1, N.d.act,
                 N.d.bn == 2 ? 1 : 0, 0, 0, params + N.bt_off};
+    }
+    // ---- the generic BatchNorm (+ activation) of any node: bn_fwd / bn_bwd on tensors as stored ----
+    // in -> the node's output (without BatchNorm parameters the activation alone)
+    int node_bn_fwd(const Node &N, const float *in, int act, hipStream_t st) const {
+        const bool bn = N.gm_off >= 0;
+        return bn_fwd(in, f(N.out_off), bn ? params + N.gm_off : nullptr, bn ? params + N.bt_off : nullptr,
+                      f(N.mean_off), f(N.istd_off), bn ? bnstats + N.rs_off : nullptr,
+                      bn ? bnstats + N.rs_off + N.C : nullptr, N.C, N.P, act, kBnEps, kBnMomentum, bnpart(), st,
+                      N.d.bn == 2 ? 1 : 0);
+    }
+    // the node's output gradient -> dst (+)= dL/d(in), and the gradients of gamma, beta and the bias it has
+    int node_bn_bwd(const Node &N, const float *in, int act, float *dst, int accum, hipStream_t st) const {
+        const bool bn = N.gm_off >= 0;
+        return bn_bwd(f(N.grad_off), f(N.out_off), in, bn ? params + N.gm_off : nullptr, f(N.mean_off), f(N.istd_off),
+                      dst, bn ? grads + N.gm_off : nullptr, bn ? grads + N.bt_off : nullptr, bias_in(grads, N), N.C, N.P,
+                      act, bnpart(), st, N.d.bn == 2 ? 1 : 0, accum, bn ? params + N.bt_off : nullptr);
     }
     // the weights the products read (W / scale under spectral norm) and the scale a weight gradient
     // divides by (NULL without spectral norm)
@@ -189,8 +216,14 @@ using Node = lrs_dipnet::Node;
 
 // a node with a conv product: weights, planes, weight and data gradients
 inline bool has_conv(const Node &N) { return N.d.kind == LRS_NODE_CONV || N.d.kind == LRS_NODE_DECODE; }
-// ... whose forward follows the CONV plan (a DECODE stage with a tail runs its own chain)
-inline bool conv_planned(const Node &N) { return has_conv(N) && !N.dec_tail; }
+
+// what follows the product: a DECODE stage that upsamples, normalises or rectifies runs the decoder's own
+// kernels on z; any other (the head) is a bias-free CONV, loss heads included
+void plan_tail(Node &N) {
+    const bool tail = N.d.kind == LRS_NODE_DECODE && (N.d.upsample || N.d.bn || N.d.act == LRS_ACT_RELU);
+    N.plan.tail = !tail ? Tail::None : N.d.upsample ? Tail::Up2Act : Tail::Act;
+    N.plan.tail_bn = tail && N.d.bn;
+}
 
 void plan_fwd(Node &N) {
     const bool on_planes = plain_unit(N.g) ? N.wpre_off >= 0 : N.col_off < 0;
@@ -206,7 +239,9 @@ void plan_bn_fwd(Node &N, bool aligned) {
     NodePlan &p = N.plan;
     const bool bn = N.d.bn != 0;
     p.nq = 0;
-    if (p.fwd == Fwd::Direct) p.bn = BnFwd::InDirect;
+    // after a tail the BatchNorm reads a as stored: nothing of the product is left to finish
+    if (p.tail != Tail::None) p.bn = p.tail_bn ? BnFwd::Generic : BnFwd::None;
+    else if (p.fwd == Fwd::Direct) p.bn = BnFwd::InDirect;
     else if (!bn && p.fwd == Fwd::Planes && plain_unit(N.g)) p.bn = BnFwd::ActInPw;
     else if (bn && (p.nq = bn_reg_q(N.P, aligned && N.P % 4 == 0)) > 0) p.bn = BnFwd::Reg;
     else p.bn = (bn && bn_one_wg(N.P)) ? BnFwd::Reduce1 : BnFwd::Generic;
@@ -215,7 +250,8 @@ void plan_bn_fwd(Node &N, bool aligned) {
 void plan_grads(Node &N) {
     N.plan.dgrad = N.d.in0 == 0 ? Dgrad::None : N.upc ? Dgrad::Upc : N.sm_dgrad ? Dgrad::Adjoint : Dgrad::Gemm;
     N.plan.wgrad = N.sm ? (N.wtab_off >= 0 ? Wgrad::Table : Wgrad::Im2colGemm) : N.upc ? Wgrad::Upc : Wgrad::Gemm;
-    N.plan.bn_bwd_fuse = N.d.bn && bn_one_wg(N.P);
+    // (a tail's BatchNorm backward takes dL/dy as stored)
+    N.plan.bn_bwd_fuse = N.plan.tail == Tail::None && N.d.bn && bn_one_wg(N.P);
 }
 
 // Sigma beside the first conv: a spectrally normalised first conv on the network input, read from
@@ -237,7 +273,7 @@ bool plan_sn_overlap(const lrs_dipnet *net) {
 // the alignment-dependent part, once the workspace is known
 void plan_bind(lrs_dipnet *net) {
     for (Node &N : net->nodes)
-        if (conv_planned(N)) plan_bn_fwd(N, al16(net->ws));
+        if (has_conv(N)) plan_bn_fwd(N, al16(net->ws));
     net->sn_overlap = plan_sn_overlap(net);
 }
 
@@ -268,15 +304,30 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
             return LRS_E_INVALID;
         if (N.d.bn < 0 || N.d.bn > 2) return LRS_E_INVALID;
         const int ci = net->tC(t0), hi = net->tH(t0), wi = net->tW(t0);
-        if (N.d.kind == LRS_NODE_CONV) {
+        if (has_conv(N)) {
+            // a DECODE stage's product is a bias-free 1x1 on the input's map; its tail may double the map
+            const bool dec = N.d.kind == LRS_NODE_DECODE;
+            const int up = dec && N.d.upsample ? 2 : 1;
             if (N.d.cout <= 0) return LRS_E_INVALID;
-            if (const int rc = make_geom(ci, hi, wi, N.d.k, N.d.stride, N.d.pad, N.d.pad_mode, N.d.upsample, N.g, &o))
+            if (dec) {
+                if (N.d.k != 1 || N.d.stride != 1 || N.d.pad != 0 || N.d.sn != 0 || N.d.bn == LRS_BN_LIP ||
+                    (N.d.upsample != 0 && N.d.upsample != LRS_UP_BILINEAR))
+                    return LRS_E_UNSUPPORTED;
+                if (N.d.act == LRS_ACT_SIGMOID && (N.d.upsample || N.d.bn)) return LRS_E_INVALID;   // the head only
+            }
+            if (const int rc = make_geom(ci, hi, wi, N.d.k, N.d.stride, N.d.pad, dec ? LRS_PAD_ZERO : N.d.pad_mode,
+                                         dec ? 0 : N.d.upsample, N.g, &o))
                 return rc;
-            N.C = N.d.cout; N.H = N.g.Ho; N.W = N.g.Wo;
+            if (dec && ((int64_t)up * hi > INT32_MAX / 4 / ((int64_t)up * wi) || N.d.cout > 65535))
+                return LRS_E_UNSUPPORTED;
+            N.C = N.d.cout; N.H = up * N.g.Ho; N.W = up * N.g.Wo;
             N.P = (int64_t)N.H * N.W;
+            const int64_t Pz = (int64_t)N.g.Ho * N.g.Wo;   // the product's map (N.P but under a doubling tail)
             N.Kc = (int64_t)ci * N.d.k * N.d.k;
             N.w_off = pofs; pofs += N.C * N.Kc;
-            N.b_off = pofs; pofs += N.C;
+            if (!dec) { N.b_off = pofs; pofs += N.C; }
+            plan_tail(N);
+            const bool tail = N.plan.tail != Tail::None;
             if (N.d.sn) {
                 if ((N.Kc < N.C ? N.Kc : N.C) > kSnMaxDim) return LRS_E_UNSUPPORTED;
                 N.sn_index = net->n_sn++;
@@ -286,7 +337,7 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
             const int64_t planes = wprep_elems(N.g, N.C, false).total();
             const bool planes_fit = planes < INT32_MAX / 3;   // k_conv_prep's 32-bit plane indices
             if (plain_unit(N.g)) {
-                if (net->implicit && pw_ok(N.g, N.C) && N.P >= kImplicitMinP && planes_fit)
+                if (net->implicit && pw_ok(N.g, N.C) && Pz >= kImplicitMinP && planes_fit)
                     N.wpre_off = ws.planes(planes);   // 1x1 on k_pw: its pre-split weight planes
             } else if (!(net->implicit && conv_implicit_ok(N.g, N.C) && N.P >= kImplicitMinP)) {
                 // col: the weight gradient's explicit im2col (written in the backward for a
@@ -312,44 +363,18 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
                 N.wpre_off = ws.planes(elems);
             }
             if (!plain_unit(N.g)) max_dcol = std::max(max_dcol, N.Kc * N.P);
-            if (N.d.bn) N.z_off = ws.floats(N.C * N.P);
-            N.gz_off = ws.floats(N.C * N.P);
-            part = std::max({part, conv_part_floats(N.g, N.C), N.upc ? upc_part_floats(N.g, N.C) : 0});
-            max_dz = std::max(max_dz, N.C * N.P);
-            plan_fwd(N);
-            plan_grads(N);
-        } else if (N.d.kind == LRS_NODE_DECODE) {
-            if (N.d.cout <= 0) return LRS_E_INVALID;
-            if (N.d.k != 1 || N.d.stride != 1 || N.d.pad != 0 || N.d.sn != 0 || N.d.bn == LRS_BN_LIP ||
-                (N.d.upsample != 0 && N.d.upsample != LRS_UP_BILINEAR))
-                return LRS_E_UNSUPPORTED;
-            if (N.d.act == LRS_ACT_SIGMOID && (N.d.upsample || N.d.bn)) return LRS_E_INVALID;   // the head only
-            if (const int rc = make_geom(ci, hi, wi, 1, 1, 0, LRS_PAD_ZERO, 0, N.g, &o)) return rc;   // the 1x1 on its own map
-            const int up = N.d.upsample ? 2 : 1;
-            if ((int64_t)up * hi > INT32_MAX / 4 / ((int64_t)up * wi) || N.d.cout > 65535) return LRS_E_UNSUPPORTED;
-            N.C = N.d.cout; N.H = up * hi; N.W = up * wi;
-            N.P = (int64_t)N.H * N.W;
-            N.Kc = ci;
-            const int64_t Plo = (int64_t)hi * wi;
-            N.w_off = pofs; pofs += N.C * N.Kc;   // (no bias: b_off stays -1)
-            N.dec_tail = N.d.upsample || N.d.bn || N.d.act == LRS_ACT_RELU;
-            const int64_t planes = wprep_elems(N.g, N.C, false).total();
-            if (net->implicit && pw_ok(N.g, N.C) && Plo >= kImplicitMinP && planes < INT32_MAX / 3)
-                N.wpre_off = ws.planes(planes);   // on k_pw, as a CONV's 1x1
-            if (N.dec_tail) {
-                N.z_off = ws.floats(N.C * Plo);
-                if (N.d.bn) {
-                    N.a_off = ws.floats(N.C * N.P);
-                    N.ga_off = ws.floats(N.C * N.P);
-                }
-            } else {
-                N.gbsink_off = ws.floats(N.C);
+            if (N.d.bn || tail) N.z_off = ws.floats(N.C * Pz);
+            if (N.plan.tail_bn) {
+                N.a_off = ws.floats(N.C * N.P);
+                N.ga_off = ws.floats(N.C * N.P);
             }
-            N.gz_off = ws.floats(N.C * Plo);
-            part = std::max(part, conv_part_floats(N.g, N.C));
+            if (dec && !tail) N.gbsink_off = ws.floats(N.C);
+            N.gz_off = ws.floats(N.C * Pz);
+            part = std::max({part, conv_part_floats(N.g, N.C), N.upc ? upc_part_floats(N.g, N.C) : 0});
+            // (dz serves a BN node on the input alone; a CONV's share stays so that no offset moves)
+            if (!dec) max_dz = std::max(max_dz, N.C * N.P);
             plan_fwd(N);
             plan_grads(N);
-            N.plan.bn_bwd_fuse = false;   // its BatchNorm backward takes dL/dy as stored (no split-K partials)
         } else if (N.d.kind == LRS_NODE_BN) {
             if (!N.d.bn) N.d.bn = 1;
             N.C = ci; N.H = hi; N.W = wi;
@@ -406,7 +431,7 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
     net->prep_off = ws.take(prep_bytes);
     net->prep_head_off = ws.take(256);   // one ConvPrep
     net->prep_side_off = ws.take(prep_bytes);
-    net->head_fusable = conv_planned(Lh) && Lh.d.bn == 0 && Lh.C <= 65535;
+    net->head_fusable = has_conv(Lh) && Lh.plan.tail == Tail::None && Lh.d.bn == 0 && Lh.C <= 65535;
     net->head_pw = net->head_fusable && plain_unit(Lh.g) && Lh.wpre_off >= 0 && Lh.P <= kHeadPwMaxP;
     if (net->head_pw) {
         net->hpart_off = ws.take(2 * (int64_t)Lh.C * ((Lh.P + 63) / 64) * 8);   // [2][C][<= ceil(P / 64) workgroups]

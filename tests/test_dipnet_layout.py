@@ -2,6 +2,7 @@
 (ca33aae): the workspace size, the parameter and running-statistics counts, every node's parameter
 offsets and every tensor's shape, for the nets and sizes the product and the benchmark use and one
 small odd size of each, with both precisions and both data-gradient forms of the upsampled convs.
+The Deep Decoder's entries (DECODERS) were recorded the same way from c4be1a1.
 
 lrs_dipnet_create needs no device, so this runs on the CPU.  The recorded table is
 tests/golden/dipnet_layout.json; it was written by loading a build of ca33aae's library:
@@ -21,7 +22,7 @@ for _p in (os.path.dirname(HERE), os.path.join(os.path.dirname(HERE), "lrs-pnp-d
         sys.path.insert(0, _p)
 
 from lrspnp import _lib  # noqa: E402
-from lrspnp.dip import DipNode, lipschitz_unet_nodes, skip_nodes  # noqa: E402
+from lrspnp.dip import DipNode, deep_decoder_nodes, lipschitz_unet_nodes, skip_nodes  # noqa: E402
 
 TABLE = os.path.join(HERE, "golden", "dipnet_layout.json")
 
@@ -32,13 +33,27 @@ SIZES = [("unet", 198, 196, 196), ("unet", 128, 36, 36), ("unet", 7, 21, 19),
 CASES = [(net, C, H, W, prec, ud) for net, C, H, W in SIZES
          for prec in (_lib.DIP_F32, _lib.DIP_SPLIT_BF16) for ud in (0, 1)]
 
+# The Deep Decoder (DECODE nodes; recorded from c4be1a1, the commit that added them, before they moved
+# onto the node plan): (channels, c_out, h, w) of the input -- the measured 196^2 x 198 configuration, a
+# 36^2 one, and a small, odd, non-square one; both precisions (it has no upsampled conv: ud = 0)
+DECODERS = [((128, 128), 198, 49, 49), ((128, 128), 128, 9, 9), ((6, 4), 5, 7, 5)]
+CASES += [("decoder", ch, cout, H, W, prec, 0) for ch, cout, H, W in DECODERS
+          for prec in (_lib.DIP_F32, _lib.DIP_SPLIT_BF16)]
+
 
 def case_id(c):
+    if c[0] == "decoder":
+        return "decoder%s-%d-%dx%d-p%d-ud%d" % (("-%d" * len(c[1])) % c[1], *c[2:])
     return "%s-%dx%dx%d-p%d-ud%d" % c
 
 
-def layout(net, C, H, W, prec, ud):
-    nodes = lipschitz_unet_nodes(C, C, 128) if net == "unet" else skip_nodes(C, C)
+def layout(net, *case):
+    if net == "decoder":
+        channels, cout, H, W, prec, ud = case
+        nodes, C = deep_decoder_nodes(channels[0], cout, channels), channels[0]
+    else:
+        C, H, W, prec, ud = case
+        nodes = lipschitz_unet_nodes(C, C, 128) if net == "unet" else skip_nodes(C, C)
     L = _lib.lib()
     arr = (DipNode * len(nodes))(*nodes)
     h = ctypes.c_void_p()

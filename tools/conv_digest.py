@@ -9,7 +9,8 @@ lrs_conv2d_bwd_x_f32 without one (upsample_dgrad 0 and 1): y, gw, gx.  Engine: t
 from seed 0 on the 36 x 36 x 7 and 66 x 66 x 7 U-Nets and the 36 x 36 x 128 skip net, each with the
 default options, with upsample_dgrad = 1 and with precision = LRS_DIP_F32 (output, parameters,
 gradients): implicit and small-map paths, split-K with S > 1 and S = 1, the parity-class convs, and
-on the 66^2 net maps that are no multiple of 4.
+on the 66^2 net maps that are no multiple of 4.  The same three steps on two Deep Decoders and their
+variants (no BatchNorm, no sigmoid, f32, a per-band mask, a frame), and one forward + backward on each.
 """
 import ctypes
 import hashlib
@@ -22,7 +23,7 @@ sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from lrspnp import _lib  # noqa: E402
-from lrspnp.dip import DipNet, lipschitz_unet_nodes, skip_nodes  # noqa: E402
+from lrspnp.dip import DipNet, deep_decoder_nodes, lipschitz_unet_nodes, skip_nodes  # noqa: E402
 from test_gpu_dip import CONV_CASES, P, S  # noqa: E402
 
 
@@ -78,3 +79,41 @@ for name, nodes, bands, hw in (("unet36x7", lipschitz_unet_nodes(7, 7, 128), 7, 
         torch.cuda.synchronize()
         for k, v in (("output", net.output()), ("params", net.params), ("grads", net.grads), ("bnstats", net.bnstats)):
             print(f"net {name} {oname} {k} {sha(v)}")
+
+# The Deep Decoder (DECODE nodes).  dec36x7: channels (128, 128), 9 x 9 -> 36 x 36 x 7: the 81- and 324-pixel
+# stages on the dense GEMM, the 1296-pixel stage and the head on k_pw, the loss head in its epilogue.
+# dec68x5: channels (16, 16), 17 x 17 -> 68 x 68 x 5: the odd width takes the scalar form of the x2 kernels,
+# the 4624-pixel head is above the fused head's limit (k_mse_head).
+# (name, channels, bands, input side, deep_decoder_nodes options, DipNet options, per-band mask, frame)
+DEC36, DEC68 = ("dec36x7", (128, 128), 7, 9), ("dec68x5", (16, 16), 5, 17)
+for (name, ch, bands, hw), oname, nkw, kw, cmask, frame in (
+        (DEC36, "default", {}, {}, False, None),
+        (DEC68, "default", {}, {}, False, None),
+        (DEC36, "nobn-lrelu", {"bn": False, "act": "lrelu"}, {}, False, None),
+        (DEC36, "nosigmoid", {"need_sigmoid": False}, {}, False, None),
+        (DEC36, "f32", {}, {"precision": _lib.DIP_F32}, False, None),
+        (DEC36, "bandmask", {}, {}, True, None),
+        (DEC68, "frame", {}, {}, False, (2, 1, 64, 66))):
+    net = DipNet(deep_decoder_nodes(ch[0], bands, ch, **nkw), ch[0], hw, hw, **kw)
+    net.init_params(0)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.rand(ch[0], hw, hw, device="cuda", generator=g) * 0.1
+    Co, Ho, Wo = net.out_shape
+    t = torch.rand(Co, Ho, Wo, device="cuda", generator=g)
+    m = (torch.rand((Co, Ho, Wo) if cmask else (Ho, Wo), device="cuda", generator=g) > 0.2).float()
+    if frame:
+        top, left, fh, fw = frame
+        net.set_frame(*frame)
+        inside = torch.zeros_like(m)
+        inside[top:top + fh, left:left + fw] = 1.0
+        m = m * inside
+    net.train_steps(x, t, m, 3, use_graph=False)
+    torch.cuda.synchronize()
+    for k, v in (("output", net.output()), ("params", net.params), ("grads", net.grads), ("bnstats", net.bnstats)):
+        print(f"net {name} {oname} {k} {sha(v)}")
+    if oname == "default":   # forward + backward from a given dL/dout: the head's own activation backward
+        gout = torch.randn(Co, Ho, Wo, device="cuda", generator=g)
+        net.forward(x)
+        net.backward(x, gout)
+        torch.cuda.synchronize()
+        print(f"net {name} fwdbwd grads {sha(net.grads)}")
