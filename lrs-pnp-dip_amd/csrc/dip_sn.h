@@ -475,7 +475,7 @@ __global__ void k_sn_apply(const SnConv *convs, const float *scale) {
 
 namespace {   // (internal linkage: this header is part of dipnet.hip's translation unit only)
 
-// The step head of the overlapped sigma (lrs_dipnet::sn_overlap): the spectral-norm Gram partials of
+// The step head of the overlapped sigma (StepPlan::sn_overlap): the spectral-norm Gram partials of
 // the n convs (blockIdx.y < n, k_sn_gram's body) and, in the extra rows blockIdx.y >= n, the first
 // conv's forward planes from the raw weights (the head ConvPrep, dip_wprep.h) with the step's loss
 // reset and Adam step count: one launch instead of two.

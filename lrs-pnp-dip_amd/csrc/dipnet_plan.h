@@ -1,9 +1,13 @@
-// DIP network engine: the net (struct lrs_dipnet), its workspace layout and the per-node plan: which
-// kernels serve a conv product's forward (a CONV's, or a DECODE stage's bias-free 1x1), the stage tail
-// after it, its BatchNorm and its two gradients.  Decided once: what the shape fixes by dipnet_layout
-// (lrs_dipnet_create), what the bound workspace's alignment fixes by plan_bind (lrs_dipnet_bind).
-// dipnet_forward, weight_grad and dipnet_backward (dipnet.hip) switch on it and evaluate no predicate of
-// their own: they ask a node's kind only to tell conv products (has_conv) from BN and CONCAT nodes.
+// DIP network engine: the net (struct lrs_dipnet), its workspace layout and its two plans.  NodePlan, per
+// node: which kernels serve a conv product's forward (a CONV's, or a DECODE stage's bias-free 1x1), the
+// stage tail after it, its BatchNorm and its two gradients.  StepPlan, per training step: the form of the
+// loss head, what opens the step, whether sigma overlaps the first conv, which conv keeps its weight
+// gradient on the main stream.  Decided once: what the shape fixes by dipnet_layout (lrs_dipnet_create),
+// what the bound workspace's alignment fixes by plan_bind (lrs_dipnet_bind); the one per-call input, the
+// alignment of the target and the mask, by step_head.
+// dipnet_forward, weight_grad, dipnet_backward and dipnet_step (dipnet_engine.h) switch on them and
+// evaluate no predicate of their own: they ask a node's kind only to tell conv products (has_conv) from BN
+// and CONCAT nodes.
 // Part of dipnet.hip's translation unit.
 #pragma once
 #include "dip_launch.h"
@@ -41,6 +45,23 @@ struct NodePlan {   // of a node with a conv product (CONV, DECODE)
     Dgrad dgrad = Dgrad::None;
     Wgrad wgrad = Wgrad::Gemm;
     bool bn_bwd_fuse = false;    // its BatchNorm backward can finish a split-K dL/dy (k_reduce_bn_bwd1)
+};
+
+enum class Head {     // the loss head of a training step
+    Pw,               // last node = 1x1 conv without BN on k_pw, small map: in that conv's epilogue (PwHead); its
+                      // per-workgroup sums go to hpart, reduced by k_head_reduce / k_head_loss on the side stream
+    Mse,              // last node = conv without BN: loss + its activation backward in one kernel (k_mse_head)
+    Generic,          // masked_mse into the last node's gradient buffer, then that node's own backward
+};
+
+struct StepPlan {     // of dipnet_step
+    Head head = Head::Generic;    // dipnet_layout; Pw may become Mse for one call (step_head)
+    bool begin_in_prep = false;   // plan_bind: the weight-preparation launch opens the step (else k_step_begin)
+    // plan_bind: sigma overlapped with the first conv: the side stream runs the spectral-norm chain and
+    // the preparation of every conv but the first, whose planes the main stream writes from the raw
+    // weights (prep_head table); its BatchNorm kernel divides by the scale (plan_sn_overlap)
+    bool sn_overlap = false;
+    int first_conv = 0;           // plan_bind: the first node with a conv product (the node count: none)
 };
 
 // ============================================================================================
@@ -83,20 +104,13 @@ struct lrs_dipnet {
     int64_t gram_off = 0, table_off = 0, misc_off = 0, bnpart_off = 0, prep_off = 0;
     int64_t part_cap = 0;     // floats of part and of part2 (the side stream's split-K partials)
     int n_prep = 0;           // convs in the per-step weight-preparation table (spectral norm and/or planes)
-    // sigma overlapped with the first conv (dipnet_step): the side stream runs the spectral-norm
-    // chain and the preparation of every conv but the first, whose planes the main stream writes from
-    // the raw weights (prep_head table); its BatchNorm kernel divides by the scale (plan_sn_overlap)
-    bool sn_overlap = false;
-    int64_t prep_head_off = 0, prep_side_off = 0;
+    StepPlan step_plan;
+    int64_t prep_head_off = 0, prep_side_off = 0;   // StepPlan::sn_overlap
     // ev_sigma right after the Lanczos (the first BatchNorm needs the scale only) and ev_prep after the
     // other convs' planes (the second conv waits for it)
     hipEvent_t ev_head = nullptr, ev_sigma = nullptr, ev_prep = nullptr;
     int64_t headcnt_off = 0;         // per-channel counters of k_mse_head (zeroed at bind, reset by the kernel)
-    bool head_fusable = false;       // last node = conv without BN: loss + its activation backward in one kernel
-    // ... and when that conv is a 1x1 on k_pw, the loss head runs in the conv's own epilogue (PwHead);
-    // its per-workgroup sums go to hpart, reduced by k_head_reduce / k_head_loss on the side stream
-    bool head_pw = false;
-    int head_nwg = 0;
+    int head_nwg = 0;                // Head::Pw
     int64_t hpart_off = 0, closs_off = 0;
     size_t ws_bytes = 0;
     int n_sn = 0;
@@ -270,11 +284,27 @@ bool plan_sn_overlap(const lrs_dipnet *net) {
     return S >= 2 && N0.P >= kForkBigP;
 }
 
-// the alignment-dependent part, once the workspace is known
+// the alignment-dependent part, once the workspace is known, and the step's
 void plan_bind(lrs_dipnet *net) {
+    StepPlan &sp = net->step_plan;
     for (Node &N : net->nodes)
         if (has_conv(N)) plan_bn_fwd(N, al16(net->ws));
-    net->sn_overlap = plan_sn_overlap(net);
+    sp.sn_overlap = plan_sn_overlap(net);
+    sp.begin_in_prep = net->n_prep > 0;
+    sp.first_conv = 0;
+    while (sp.first_conv < (int)net->nodes.size() && !has_conv(net->nodes[sp.first_conv])) ++sp.first_conv;
+}
+
+// float4 mask loads: row c starts at mask + c * mstride, 16-B aligned for every c when the base is
+// and the stride is a multiple of 4 floats (0, or P with P % 4 == 0)
+bool mask_al16(const float *mask, int64_t mstride) { return !mask || (al16(mask) && mstride % 4 == 0); }
+
+// The loss head of one call: k_pw's epilogue takes its float4 form when P % 4 == 0 and reads the target
+// and the mask rows as float4 there; a [C][P] mask with P % 4 != 0 has unaligned rows and takes
+// k_mse_head's scalar path instead, as does any unaligned target or mask.
+Head step_head(const lrs_dipnet *net, const float *target, const float *mask, int64_t mstride) {
+    const Head h = net->step_plan.head;
+    return (h == Head::Pw && !(mask_al16(mask, mstride) && al16(target))) ? Head::Mse : h;
 }
 
 // ---- the workspace layout -------------------------------------------------------------------
@@ -431,9 +461,10 @@ int dipnet_layout(lrs_dipnet *net, const lrs_dip_node *nodes, int n_nodes) {
     net->prep_off = ws.take(prep_bytes);
     net->prep_head_off = ws.take(256);   // one ConvPrep
     net->prep_side_off = ws.take(prep_bytes);
-    net->head_fusable = has_conv(Lh) && Lh.plan.tail == Tail::None && Lh.d.bn == 0 && Lh.C <= 65535;
-    net->head_pw = net->head_fusable && plain_unit(Lh.g) && Lh.wpre_off >= 0 && Lh.P <= kHeadPwMaxP;
-    if (net->head_pw) {
+    const bool head_mse = has_conv(Lh) && Lh.plan.tail == Tail::None && Lh.d.bn == 0 && Lh.C <= 65535;
+    const bool head_pw = head_mse && plain_unit(Lh.g) && Lh.wpre_off >= 0 && Lh.P <= kHeadPwMaxP;
+    net->step_plan.head = head_pw ? Head::Pw : head_mse ? Head::Mse : Head::Generic;
+    if (head_pw) {
         net->hpart_off = ws.take(2 * (int64_t)Lh.C * ((Lh.P + 63) / 64) * 8);   // [2][C][<= ceil(P / 64) workgroups]
         net->closs_off = ws.take((int64_t)Lh.C * 8);
     }

@@ -11,6 +11,11 @@ default options, with upsample_dgrad = 1 and with precision = LRS_DIP_F32 (outpu
 gradients): implicit and small-map paths, split-K with S > 1 and S = 1, the parity-class convs, and
 on the 66^2 net maps that are no multiple of 4.  The same three steps on two Deep Decoders and their
 variants (no BatchNorm, no sigmoid, f32, a per-band mask, a frame), and one forward + backward on each.
+Then every form of the training step (StepPlan, dipnet_plan.h) the nets above leave out: the overlapped
+sigma (a 196 x 196 x 7 U-Net of hidden width OVERLAP_HIDDEN, eager and as a replayed graph), the loss head
+demoted from k_pw's epilogue by a misaligned mask, a net whose last node is a BatchNorm (the generic
+head), early stopping with and without a frame (the ring and the state too), and a stand-alone forward +
+backward on a U-Net.  (The 36^2 U-Net above has the head in k_pw's epilogue, the 66^2 one k_mse_head.)
 """
 import ctypes
 import hashlib
@@ -23,7 +28,8 @@ sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from lrspnp import _lib  # noqa: E402
-from lrspnp.dip import DipNet, deep_decoder_nodes, lipschitz_unet_nodes, skip_nodes  # noqa: E402
+from lrspnp.dip import (ACT_NONE, BN_NONE, BN_PLAIN, NODE_BN, DipNet, DipNode, EarlyStopper, conv_node,  # noqa: E402
+                        deep_decoder_nodes, lipschitz_unet_nodes, skip_nodes)
 from test_gpu_dip import CONV_CASES, P, S  # noqa: E402
 
 
@@ -117,3 +123,59 @@ for (name, ch, bands, hw), oname, nkw, kw, cmask, frame in (
         net.backward(x, gout)
         torch.cuda.synchronize()
         print(f"net {name} fwdbwd grads {sha(net.grads)}")
+
+
+# ---- the step's forms ----------------------------------------------------------------------------
+# the narrowest U-Net that takes the overlapped sigma at 196^2 (k_sn_gram_head in a kernel trace); its
+# first conv's map is 98^2, the smallest that does
+OVERLAP_HIDDEN = 16
+
+
+def step_case(tag, nodes, cin, hw, use_graph=False, shift_mask=False, frame=None, es=False, fwdbwd=False):
+    net = DipNet(nodes, cin, hw, hw)
+    net.init_params(0)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.rand(cin, hw, hw, device="cuda", generator=g)
+    Co, Ho, Wo = net.out_shape
+    t = torch.rand(Co, Ho, Wo, device="cuda", generator=g)
+    m = (torch.rand(Ho, Wo, device="cuda", generator=g) > 0.2).float()
+    if frame:
+        top, left, fh, fw = frame
+        net.set_frame(*frame)
+        inside = torch.zeros_like(m)
+        inside[top:top + fh, left:left + fw] = 1.0
+        m = m * inside
+    if shift_mask:   # the same mask one float into its storage: no longer 16-byte aligned
+        store = torch.zeros(Ho * Wo + 1, device="cuda")
+        store[1:] = m.flatten()
+        m = store[1:].view(Ho, Wo)
+        assert m.data_ptr() % 16 == 4
+    stopper = EarlyStopper(Co * net.frame[2] * net.frame[3], size=2, patience=60) if es else None
+    if fwdbwd:
+        net.forward(x)
+        net.backward(x, torch.randn(Co, Ho, Wo, device="cuda", generator=g))
+    else:
+        net.train_steps(x, t, m, 3, es=stopper, use_graph=use_graph)
+    torch.cuda.synchronize()
+    out = [("output", net.output()), ("params", net.params), ("grads", net.grads), ("bnstats", net.bnstats)]
+    if es:
+        out += [("es_ring", stopper.ring), ("es_state", stopper.state)]
+    for k, v in out:
+        print(f"step {tag} {k} {sha(v)}")
+
+
+def bn_node(src):
+    return DipNode(NODE_BN, src, 0, 0, 0, 0, 0, 0, 0, BN_PLAIN, ACT_NONE, 0, 0)
+
+
+unet196 = lipschitz_unet_nodes(7, 7, OVERLAP_HIDDEN)
+unet36 = lipschitz_unet_nodes(7, 7, 128)
+step_case(f"overlap unet196x7h{OVERLAP_HIDDEN} eager", unet196, 7, 196)
+step_case(f"overlap unet196x7h{OVERLAP_HIDDEN} graph", unet196, 7, 196, use_graph=True)
+step_case("demoted unet36x7 mask+4B", unet36, 7, 36, shift_mask=True)
+step_case("generic bn8x7", [bn_node(0)], 7, 8)
+step_case("generic convbn8x7", [conv_node(0, 0, 8, 3, bn=BN_NONE, act=ACT_NONE, sn=0), bn_node(1)], 7, 8)
+step_case("es unet36x7", unet36, 7, 36, es=True)
+step_case("es unet36x7 frame", unet36, 7, 36, es=True, frame=(2, 1, 32, 34))
+step_case("es unet36x7 graph", unet36, 7, 36, es=True, use_graph=True)
+step_case("fwdbwd unet36x7", unet36, 7, 36, fwdbwd=True)
