@@ -422,6 +422,25 @@ int lrs_masked_mse_cmask_f32(const float *out, const float *target, const float 
  * lrs_masked_mse_cmask_f32, launch for launch. */
 int lrs_masked_mse_framed_f32(const float *out, const float *target, const float *mask, int mask_channels,
                               int C, int64_t P, int64_t n_mean, float *gout, double *loss_acc, void *stream);
+/* Smoothness term on the net's output, an extension (the reference's loss is the masked MSE alone;
+ * admm_utils.py carries a tv_prox it never calls): anisotropic spatial TV, band TV and spatial-spectral TV
+ * (SSTV) of the image o = the H x W pixels at (top, left) of out[C][Hf][Wf].  With N = n_mean and
+ * phi(d) = sqrt(d^2 + eps^2) (|d| for eps = 0):
+ *   R(o) = (w_sp / N) sum [ phi(o[c,y+1,x] - o[c,y,x]) + phi(o[c,y,x+1] - o[c,y,x]) ]
+ *        + (w_bd / N) sum   phi(o[c+1,y,x] - o[c,y,x])
+ *        + (w_ss / N) sum [ phi(Dy Dc o) + phi(Dx Dc o) ],
+ *   Dy Dc o[c,y,x] = (o[c+1,y+1,x] - o[c,y+1,x]) - (o[c+1,y,x] - o[c,y,x]), Dx Dc likewise along x,
+ * each sum over the indices whose operands all lie inside the image (empty for C, H or W = 1): nothing is
+ * padded, and nothing of the frame is used.  gout (nullable, the layout of out) += dR/do on the image, its
+ * frame untouched, with phi'(d) = d / sqrt(d^2 + eps^2), for eps = 0 sign(d) with sign(0) = 0; a gather in a
+ * fixed order (no atomics: reruns are bit-identical).  loss_acc (nullable, device double) += N R, so that
+ * after lrs_masked_mse_framed_f32 on the same gout and accumulator, gout is dL/dout of masked MSE + R --
+ * what lrs_dipnet_backward takes -- and loss_acc / N that loss.  (lrs_dipnet_train_steps* train on the masked
+ * MSE alone.)
+ * LRS_E_INVALID: out NULL, a size <= 0, an image that does not fit the frame, a negative weight or eps,
+ * n_mean <= 0.  All three weights 0: LRS_OK, nothing is launched. */
+int lrs_sstv_f32(const float *out, int C, int Hf, int Wf, int top, int left, int H, int W, float w_sp, float w_bd,
+                 float w_ss, float eps, int64_t n_mean, float *gout, double *loss_acc, void *stream);
 
 /* Layout transforms between the unfolded matrix X[p = i + H j][b] and the DIP image img[b][i][j]
  * (…1-LiP.py:404 DIP_input = X + (1/mu_2) lambda_2 as (1,B,H,W); :411 U back to (P,B)). */

@@ -6,11 +6,13 @@
 // step in a hipGraph and replay it: the Adam step count and the early-stopping state live in
 // device memory, so a replayed step is exactly the eager step.
 // dip_launch.h: geometry and the kernel launchers; dipnet_plan.h: the net, its layout and its plans;
-// dipnet_engine.h: the forward, the backward and the step.  This file holds the C entry points.
+// dipnet_engine.h: the forward, the backward and the step; dip_tv.h: the stand-alone TV term of the output
+// (lrs_sstv_f32).  This file holds the C entry points.
 // Every node with a conv product (CONV, and the Deep Decoder's DECODE) runs one path: product -> the
 // stage tail the plan names (DECODE: [bilinear x2 +] activation) -> BatchNorm; a node's generic
 // BatchNorm call is lrs_dipnet::node_bn_fwd / node_bn_bwd, a bias that may be absent bias_in.
 #include "dipnet_engine.h"
+#include "dip_tv.h"
 
 // Dense fp32-accurate GEMM for the library's other components (the K > 512 ISTA path,
 // ista_generic.hip; declared in ista_paths.h):
@@ -254,6 +256,12 @@ extern "C" int lrs_masked_mse_framed_f32(const float *out, const float *target, 
                                          int C, int64_t P, int64_t n_mean, float *gout, double *loss_acc,
                                          void *stream) {
     return masked_mse(out, target, mask, mask_channels, C, P, n_mean, gout, loss_acc, stream);
+}
+
+extern "C" int lrs_sstv_f32(const float *out, int C, int Hf, int Wf, int top, int left, int H, int W, float w_sp,
+                            float w_bd, float w_ss, float eps, int64_t n_mean, float *gout, double *loss_acc,
+                            void *stream) {
+    return sstv(out, C, Hf, Wf, top, left, H, W, w_sp, w_bd, w_ss, eps, n_mean, gout, loss_acc, (hipStream_t)stream);
 }
 
 extern "C" int lrs_masked_mse_f32(const float *out, const float *target, const float *mask, int C, int64_t P,

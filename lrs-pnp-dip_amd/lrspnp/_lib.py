@@ -70,6 +70,8 @@ _PER_BAND_MASK = ("lrs_masked_mse_cmask_f32", "lrs_dipnet_train_steps_cmask")
 # ... and the ones of the reflected frame (images of a size the DIP net does not reproduce)
 _FRAME = ("lrs_masked_mse_framed_f32", "lrs_unfolded_to_frame_f32", "lrs_frame_to_unfolded_f32",
           "lrs_dipnet_set_frame", "lrs_dipnet_get_frame")
+# ... and the TV term of the DIP output
+_TV = ("lrs_sstv_f32",)
 
 
 def build(force: bool = False) -> str:
@@ -156,6 +158,7 @@ def _declare(L):
         "lrs_frame_to_unfolded_f32": (i32, [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp]),
         "lrs_dipnet_set_frame": (i32, [vp, i32, i32, i32, i32]),
         "lrs_dipnet_get_frame": (i32, [vp] + [c.POINTER(c.c_int)] * 4),
+        "lrs_sstv_f32": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, i64, vp, vp, vp]),
         "lrs_es_ring_bytes": (sz, [i32, i64]),
         "lrs_es_init": (i32, [vp, i32, i32, vp]),
         "lrs_es_update_f32": (i32, [vp, i64, vp, vp, vp]),
@@ -184,7 +187,7 @@ def _declare(L):
         "lrs_stream_wait": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
-        if name in _PER_BAND_MASK + _FRAME and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
+        if name in _PER_BAND_MASK + _FRAME + _TV and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
             continue   # an A/B build from before these: its other paths still time against this one
         fn = getattr(L, name)
         fn.restype = res

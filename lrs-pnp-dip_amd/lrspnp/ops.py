@@ -15,7 +15,7 @@ from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLA
                    SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, LrsError, check, device_lib, ista_accel, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -517,3 +517,34 @@ def masked_mse(out, target, mask=None, want_grad: bool = True, stream=None, n_me
         check(Ld.lrs_masked_mse_framed_f32(_p(out), _p(target), _p(mask), mc, C, P, int(n_mean), _p(gout), _p(acc),
                                            _s(stream)), "lrs_masked_mse_framed_f32")
         return acc / int(n_mean), gout
+
+
+def sstv(out, gout=None, loss_acc=None, frame=None, spatial: float = 0.0, band: float = 0.0, sstv: float = 0.0,
+         eps: float = 0.0, n_mean: int | None = None, stream=None):
+    """The smoothness term R of lrs_sstv_f32 on the image inside out (C, Hf, Wf): spatial TV, band TV and
+    spatial-spectral TV with weights spatial / band / sstv, phi(d) = sqrt(d^2 + eps^2) (include/lrspnp.h).
+    frame: (top, left, H, W) of the image, None = the whole of out.  n_mean: the N the sums are divided by
+    (default the image's C*H*W).
+    gout (C, Hf, Wf) += dR/do on the image (None: a new zero tensor, so the result is dR/do itself);
+    loss_acc (float64, 1 element) += N * R (None: a new zero accumulator).
+    Returns (loss_acc / N as a float64 device tensor, gout)."""
+    Ld = device_lib()
+    _dev(out, torch.float32, "out")
+    if out.dim() != 3:
+        raise LrsError(f"out {tuple(out.shape)} must be (C, Hf, Wf)")
+    C, Hf, Wf = out.shape
+    top, left, H, W = (0, 0, Hf, Wf) if frame is None else (int(v) for v in frame)
+    n = C * H * W if n_mean is None else int(n_mean)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        if gout is None:
+            gout = torch.zeros_like(out)
+        if loss_acc is None:
+            loss_acc = torch.zeros(1, dtype=torch.float64, device=out.device)
+        _dev(gout, torch.float32, "gout")
+        _dev(loss_acc, torch.float64, "loss_acc")
+        if gout.shape != out.shape or loss_acc.numel() != 1:
+            raise LrsError(f"gout {tuple(gout.shape)} must have out's shape {tuple(out.shape)} and loss_acc one element")
+        check(Ld.lrs_sstv_f32(_p(out), C, Hf, Wf, top, left, H, W, ctypes.c_float(spatial), ctypes.c_float(band),
+                              ctypes.c_float(sstv), ctypes.c_float(eps), n, _p(gout), _p(loss_acc), _s(stream)),
+              "lrs_sstv_f32")
+        return loss_acc / n, gout
