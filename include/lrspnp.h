@@ -297,6 +297,40 @@ int lrs_svt_finish_f32(const float *X, const float *L2, float c2, int64_t P, int
  * stage is that path: LRS_E_UNSUPPORTED there. Host-only, no device access. */
 int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, int64_t *ld);
 
+/* ---- TV prox on the cube: a learning-free choice for the low-rank slot -----------------------
+ * An extension (the reference's U update is the SVT or a DIP; admm_utils.py carries a tv_prox it never
+ * calls).  X, L2, U are [P][B] as for the SVT, P = H W, p = i + H j, and the image is
+ * o[c = b][y = i][x = j] (lrs_unfolded_to_image_f32's map).  With Z = fl(X + fl(c2 L2)) (L2 nullable):
+ *   U = argmin_u 1/2 ||u - Z||^2 + tau T(u)
+ *   T(u) = w_sp sum(|Dy u| + |Dx u|) + w_bd sum |Dc u| + w_ss sum(|Dy Dc u| + |Dx Dc u|),
+ * the operators, their association and their index sets those of lrs_sstv_f32 below: T(u) is N R of that
+ * call with eps = 0.  Any H, W, B with H W B < 2^31 (LRS_E_UNSUPPORTED from there on).
+ * The algorithm is fixed: n_iter iterations of the fast gradient projection on the dual (Beck-Teboulle
+ * FGP) in fp32.  K stacks the operators whose weight is > 0, the box radii are r = (float)(tau w), the step
+ * is the fp32 1 / L, L = 8 [w_sp > 0] + 4 [w_bd > 0] + 32 [w_ss > 0] >= ||K||^2:
+ *   p = 0, q = p, t = 1;  n_iter times:  u = Z - K^T q;  p_new = clip(q + (1/L) K u, -r, r);
+ *   t_new = (1 + sqrt(1 + 4 t^2)) / 2, beta = (float)((t - 1) / t_new) (fp64 on the host, as
+ *   LRS_ISTA_ACCEL_FISTA);  q = p_new + beta (p_new - p);  then U = Z - K^T p.
+ * K^T is a gather in a fixed order without float atomics: reruns are bit-identical, and so are calls whose
+ * bases are aligned differently.  Two launches per iteration on the caller's stream; the call never
+ * allocates and never synchronises, and every refusal is decided on the host before a launch.
+ * stats (nullable, device, 2 doubles): the primal objective 1/2 ||U - Z||^2 + tau T(U) and the duality gap
+ * sum_f r_f |K_f U| - <p, K U> of the returned pair, as fp64 sums in a fixed order: how a caller chooses
+ * n_iter.  All weights 0, tau = 0 or n_iter = 0: U = Z by one copy kernel, and stats is the pair (Z, p = 0)'s,
+ * {tau T(Z), tau T(Z)} -- {0, 0} unless only n_iter is 0.
+ * flags: LRS_TVPROX_WARM starts from the p the previous call left in the same ws, clipped to this call's
+ * radii, with the momentum reset (t = 1).  The caller guarantees that that call had the same (H, W, B) and
+ * the same set of weights > 0, and ran at least one iteration; without the flag the contents of ws are
+ * ignored.  ws: lrs_tvprox_workspace bytes (for all five fields whatever the weights; 0: a size <= 0 or
+ * H W B >= 2^31), 16-byte aligned for the vector forms.  U may alias neither X nor L2.
+ * LRS_E_INVALID: X, U or ws NULL, a size <= 0, a negative or NaN weight or tau, n_iter < 0, unknown flag
+ * bits.  LRS_E_WORKSPACE: ws_bytes too small. */
+#define LRS_TVPROX_WARM 1
+size_t lrs_tvprox_workspace(int64_t H, int64_t W, int64_t B);
+int lrs_tvprox_f32(const float *X, const float *L2, float c2, int64_t H, int64_t W, int64_t B, float w_sp,
+                   float w_bd, float w_ss, double tau, int n_iter, int flags, float *U, double *stats, void *ws,
+                   size_t ws_bytes, void *stream);
+
 /* ---- col2im + closed-form X update + dual updates ------------------------------------------
  * IMout = sum over covering blocks (block order) of phi, Weight = count, lambda1_sum = repeated
  * sum of lambda_1, then (float32, the reference's operation order)

@@ -35,6 +35,8 @@ ISTA_ACCEL = {"off": ISTA_ACCEL_NONE, "fista": ISTA_ACCEL_FISTA}
 
 # flag word (`warm`) of the SVT calls
 SVT_WARM, SVT_JACOBI, SVT_MULTI_WG, SVT_WIDE_TRI, SVT_WIDE_MW = 1, 2, 4, 8, 16
+# flag word of lrs_tvprox_f32
+TVPROX_WARM = 1
 
 
 class IstaOpts(ctypes.Structure):
@@ -70,8 +72,8 @@ _PER_BAND_MASK = ("lrs_masked_mse_cmask_f32", "lrs_dipnet_train_steps_cmask")
 # ... and the ones of the reflected frame (images of a size the DIP net does not reproduce)
 _FRAME = ("lrs_masked_mse_framed_f32", "lrs_unfolded_to_frame_f32", "lrs_frame_to_unfolded_f32",
           "lrs_dipnet_set_frame", "lrs_dipnet_get_frame")
-# ... and the TV term of the DIP output
-_TV = ("lrs_sstv_f32",)
+# ... and the TV term of the DIP output and the TV prox on the cube
+_TV = ("lrs_sstv_f32", "lrs_tvprox_workspace", "lrs_tvprox_f32")
 
 
 def build(force: bool = False) -> str:
@@ -125,6 +127,8 @@ def _declare(L):
         "lrs_svt_gram_offset": (i32, [i64, i64, vp, vp]),
         "lrs_diag_svt_state": (i32, [vp, i64, i64, vp]),
         "lrs_diag_svt_apply": (i32, [vp, vp, f32, i64, i64, vp, vp, vp]),
+        "lrs_tvprox_workspace": (sz, [i64, i64, i64]),
+        "lrs_tvprox_f32": (i32, [vp, vp, f32, i64, i64, i64, f32, f32, f32, f64, i32, i32, vp, vp, vp, sz, vp]),
         "lrs_admm_update_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, vp, vp,
                                       vp, vp, f32, f32, f32, vp, vp, vp]),
         # DIP low-rank prox

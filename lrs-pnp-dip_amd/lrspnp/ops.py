@@ -12,10 +12,10 @@ import torch
 
 from . import _lib as _libmod
 from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLAB, PROX_SOFT, SVT_JACOBI, SVT_MULTI_WG,
-                   SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, LrsError, check, device_lib, ista_accel, lib)
+                   SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, TVPROX_WARM, LrsError, check, device_lib, ista_accel, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "tvprox_workspace", "tvprox", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -408,6 +408,46 @@ def svt_apply_only(X, L2, c2: float, ws, U, stream=None):
     P, B = X.shape
     check(device_lib().lrs_diag_svt_apply(_p(X), _p(L2), float(c2), P, B, _p(ws), _p(U), _s(stream)),
           "lrs_diag_svt_apply")
+    return U
+
+
+def tvprox_workspace(H: int, W: int, B: int, device) -> torch.Tensor:
+    """Device workspace of tvprox() for an H x W image with B bands (lrs_tvprox_workspace: all five dual
+    fields whatever the weights)."""
+    n = int(lib().lrs_tvprox_workspace(int(H), int(W), int(B)))
+    if n == 0:
+        raise LrsError(f"lrs_tvprox_workspace: sizes not served (H {H}, W {W}, B {B}; positive, H*W*B < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def tvprox(X, L2, c2: float, H: int, W: int, ws, U=None, w_sp: float = 0.0, w_bd: float = 0.0, w_ss: float = 0.0,
+           tau: float = 0.0, n_iter: int = 0, warm: bool = False, stats=None, stream=None):
+    """U = argmin_u 1/2 ||u - Z||^2 + tau T(u), Z = X + c2*L2 (L2 may be None), T the spatial / band /
+    spatial-spectral TV of the cube with weights w_sp / w_bd / w_ss: n_iter iterations of the fast gradient
+    projection on the dual (lrs_tvprox_f32, include/lrspnp.h).  X (P, B) with P = H*W, p = i + H*j.
+    warm: start from the dual variable the previous call left in `ws` (same sizes, same weights > 0).
+    stats: a float64 device tensor of 2 elements that receives the primal objective and the duality gap.
+    Returns U."""
+    L = device_lib()
+    _dev(X, torch.float32, "X")
+    if L2 is not None:
+        _dev(L2, torch.float32, "L2")
+    _dev(ws, torch.uint8, "ws")
+    P, B = X.shape
+    if P != H * W:
+        raise LrsError(f"P = {P} != H*W = {H * W}")
+    if U is None:
+        U = torch.empty_like(X)
+    _dev(U, torch.float32, "U")
+    if U.shape != X.shape or (L2 is not None and L2.shape != X.shape):
+        raise LrsError(f"U {tuple(U.shape)} and L2 must have X's shape {tuple(X.shape)}")
+    if stats is not None:
+        _dev(stats, torch.float64, "stats")
+        if stats.numel() != 2:
+            raise LrsError("stats must hold 2 doubles")
+    check(L.lrs_tvprox_f32(_p(X), _p(L2), float(c2), int(H), int(W), B, float(w_sp), float(w_bd), float(w_ss),
+                           float(tau), int(n_iter), TVPROX_WARM if warm else 0, _p(U), _p(stats), _p(ws), ws.numel(),
+                           _s(stream)), "lrs_tvprox_f32")
     return U
 
 

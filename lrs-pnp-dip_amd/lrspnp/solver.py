@@ -22,6 +22,18 @@ from .dip import stream_wait
 
 
 @dataclass
+class TvProxConfig:
+    """lowrank='tv': the weights of the cube's spatial, band and spatial-spectral TV in U = prox_{T / mu2}
+    (ops.tvprox), the fixed number of dual iterations per outer iteration, and whether an outer iteration
+    starts from the previous one's dual variable.  A starting point: no quality claim rests on these values."""
+    w_sp: float = 0.0
+    w_bd: float = 0.0
+    w_ss: float = 1.0
+    n_iter: int = 20
+    warm: bool = True
+
+
+@dataclass
 class LrsPnPConfig:
     """The knob table of SURVEY.md §5 (main_LRS_PnP.py:218-238 defaults)."""
     gamma: float = 0.5            # data fidelity                      main_LRS_PnP.py:218
@@ -44,8 +56,9 @@ class LrsPnPConfig:
     # one-workgroup Jacobi chain, 'tri', the tridiagonal chain over many workgroups (LRS_SVT_WIDE_TRI), or
     # 'tri-mw', that chain with its Householder reduction over many workgroups too (+ LRS_SVT_WIDE_MW)
     svt_wide_solver: str = "jacobi"
-    lowrank: str = "svt"          # 'svt' (main_LRS_PnP.py:315) or 'dip' (…1-LiP.py:399-411)
+    lowrank: str = "svt"          # 'svt' (main_LRS_PnP.py:315), 'dip' (…1-LiP.py:399-411) or 'tv' (TV prox on the cube)
     dip: object = None            # lrspnp.dip.DipConfig for lowrank='dip' (None: reference defaults)
+    tv: object = None             # TvProxConfig for lowrank='tv' (None: its defaults); the dip fields are ignored there
     dip_seed: int = 0             # DIP init seed of outer iteration t is dip_seed + t
     # Workgroups of the sparse-coding kernel beside the DIP training (lowrank='dip';
     # lrs_ista_opts.max_workgroups, 0 = one per 16-block tile).  Measured at configs[2]
@@ -258,8 +271,17 @@ class LrsPnP:
             self.gram = ops.svt_gram_view(self.svt_ws, self.P, self.B) if comm is not None else None
         elif cfg.lowrank == "dip":
             self._init_dip(image_shape, dev, engine=dip_engine)
+        elif cfg.lowrank == "tv":
+            if image_shape is None:
+                raise LrsError("lowrank='tv' needs image_shape=(H, W) with H*W = P")
+            H, W = (int(v) for v in image_shape)
+            if H * W != self.P:
+                raise LrsError(f"image_shape {H}x{W} does not match P = {self.P}")
+            self.H, self.W = H, W
+            self.tv = cfg.tv or TvProxConfig()
+            self.tv_ws = ops.tvprox_workspace(H, W, self.B, dev)
         else:
-            raise LrsError(f"unknown lowrank prox {cfg.lowrank!r}")
+            raise LrsError(f"unknown lowrank prox {cfg.lowrank!r} (svt | dip | tv)")
 
     def _init_dip(self, image_shape, dev, engine=True):
         """DIP target = the observed cube as an image, mask_bkg = the pixel mask
@@ -342,6 +364,13 @@ class LrsPnP:
                         stream=stream or torch.cuda.current_stream())
         self.iteration += 1
 
+    def low_rank_tv(self, stream=None, stats=None):
+        """U = prox_{tau T}(X + L2/mu2), tau = 1/mu2 as the SVT's, on `stream` (ops.tvprox)."""
+        tv = self.tv
+        return ops.tvprox(self.X, self.L2, self.c2, self.H, self.W, self.tv_ws, U=self.U, w_sp=tv.w_sp, w_bd=tv.w_bd,
+                          w_ss=tv.w_ss, tau=self.tau, n_iter=tv.n_iter, warm=tv.warm and self.iteration > 0,
+                          stats=stats, stream=stream)
+
     def low_rank(self, stream=None, s_out=None):
         warm = self.cfg.svt_warm and self.iteration > 0
         return ops.svt(self.X, self.L2, self.c2, self.tau, self.svt_ws, U=self.U, s_out=s_out, warm=warm,
@@ -369,11 +398,13 @@ class LrsPnP:
 
     def step(self):
         """One outer ADMM iteration (main_LRS_PnP.py:250-366), stream-ordered.  No host sync in
-        the SVT mode; the DIP mode polls its early-stopping flag on the low-rank stream only."""
+        the SVT and TV modes; the DIP mode polls its early-stopping flag on the low-rank stream only."""
         if self.cfg.lowrank == "dip":
             if self.dip is None:
                 raise LrsError("this LrsPnP was built without a DIP engine (dip_engine=False)")
             return self._step_dip()
+        if self.cfg.lowrank == "tv":
+            return self._step_tv()
         main = torch.cuda.current_stream()
         lr = self.lowrank_stream
         warm = self.cfg.svt_warm and self.iteration > 0
@@ -398,6 +429,20 @@ class LrsPnP:
             # solve starts at once; the tridiagonal chain fits inside the sparse coding even when
             # its Gram waits for the first sparse-coding workgroups to retire
             main.wait_event(gram_done)
+        self._ista(self.cfg.Nit, main)
+        stream_wait(main, lr)
+        ops.admm_update(self.X, self.L1, self.L2, self.Y, self.M, self.U, self.phi, self.cfg.bb, self.grid,
+                        self.gamma32, self.mu1_32, self.mu2_32, norms=self.norms, stream=main)
+        self.iteration += 1
+
+    def _step_tv(self):
+        main = torch.cuda.current_stream()
+        lr = self.lowrank_stream
+        stream_wait(lr, main)
+        # the TV prox's stencil passes run beside im2col and the sparse coding; no host sync
+        self.low_rank_tv(lr)
+        ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
+                   stream=main)
         self._ista(self.cfg.Nit, main)
         stream_wait(main, lr)
         ops.admm_update(self.X, self.L1, self.L2, self.Y, self.M, self.U, self.phi, self.cfg.bb, self.grid,
