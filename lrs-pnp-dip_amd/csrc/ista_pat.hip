@@ -144,16 +144,8 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
     const int32_t *tiles = p.plan + p.nb;
     const int voff = lane * 16;
     const int img_bytes = NT * NQ * 1024;
-    const __amdgpu_buffer_rsrc_t rDA = __builtin_amdgcn_make_buffer_rsrc((void *)p.DAf, 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rDT = __builtin_amdgcn_make_buffer_rsrc((void *)p.DTf, 0, img_bytes, 0x00020000);
-    auto gq = [&](const floatx4 &G, float4 a, const float (&r)[4]) -> floatx4 {
-        floatx4 acc = G;
-        acc = mfma16x16x4(a.x, r[0], acc);
-        acc = mfma16x16x4(a.y, r[1], acc);
-        acc = mfma16x16x4(a.z, r[2], acc);
-        acc = mfma16x16x4(a.w, r[3], acc);
-        return acc;
-    };
+    const __amdgpu_buffer_rsrc_t rDA = ista_image(p.DAf, img_bytes);
+    const __amdgpu_buffer_rsrc_t rDT = ista_image(p.DTf, img_bytes);
 
     // XCD-aware tile order: workgroup b runs on XCD b % 8 (round-robin dispatch), so with one
     // workgroup per tile XCD x takes the x-th contiguous eighth of the (pattern-major) tile list and
@@ -210,14 +202,13 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
 #pragma unroll
             for (int o = 0; o < NOWN; ++o) {
                 const auto v = __builtin_amdgcn_raw_buffer_load_b128(rDT, voff, (t * NQ + w + S * o) * 1024, 0);
-                bown[o] = gq(bown[o], __builtin_bit_cast(float4, v), r);
+                bown[o] = mfma_chain(bown[o], __builtin_bit_cast(float4, v), r);
             }
         }
 
         // Q fragments of this wave in iteration order k = kq NOWN + o (the same sequence every
         // iteration, so the ring runs on across iterations)
-        const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(p.QAf + (int64_t)pat * NQ * NQ * 64), 0, NQ * NQ * 1024, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rQ = ista_image(p.QAf + (int64_t)pat * NQ * NQ * 64, NQ * NQ * 1024);
         auto qfrag = [&](int k) -> float4 {
             const int kq = k / NOWN, o = k - kq * NOWN;
             return __builtin_bit_cast(float4,
@@ -242,23 +233,19 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
                     const int k = kq * NOWN + o;
                     const float4 a = ring[k % RING];
                     ring[k % RING] = qfrag((k + RING) % NFRAG);
-                    acc[o] = mfma16x16x4(a.x, xv[0], acc[o]);
-                    acc[o] = mfma16x16x4(a.y, xv[1], acc[o]);
-                    acc[o] = mfma16x16x4(a.z, xv[2], acc[o]);
-                    acc[o] = mfma16x16x4(a.w, xv[3], acc[o]);
+                    acc[o] = mfma_chain(acc[o], a, xv);
                 }
             }
             // g = x + (b - Q x) / alpha of the owned tiles -> gbuf
 #pragma unroll
             for (int o = 0; o < NOWN; ++o) {
                 const int q = w + S * o;
-                const floatx4 xo = xbuf[q * 64 + lane];
-                float4 gr;
-                gr.x = xo[0] + rs_div(bown[o][0] - acc[o][0], al, ral);
-                gr.y = xo[1] + rs_div(bown[o][1] - acc[o][1], al, ral);
-                gr.z = xo[2] + rs_div(bown[o][2] - acc[o][2], al, ral);
-                gr.w = xo[3] + rs_div(bown[o][3] - acc[o][3], al, ral);
-                *reinterpret_cast<float4 *>(&gbuf[jl * KP + gsw(jl, 16 * q + 4 * g)]) = gr;
+                // b - Q x element by element: as the vector difference bown[o] - acc[o] six forms compile differently
+                *reinterpret_cast<float4 *>(&gbuf[jl * KP + gsw(jl, 16 * q + 4 * g)]) =
+                    ista_grad4(xbuf[q * 64 + lane],
+                               floatx4{bown[o][0] - acc[o][0], bown[o][1] - acc[o][1], bown[o][2] - acc[o][2],
+                                       bown[o][3] - acc[o][3]},
+                               al, ral);
             }
             __syncthreads();   // every wave's products have read x; the gradient rows are complete
 
@@ -288,15 +275,15 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
             }
             if constexpr (ACCEL) {
                 // ---- momentum on the owned tiles: xbuf <- z_{k+1}, but x_Nit itself after the last prox ----
-                const double tn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * tk * tk));
-                const float beta = (float)((tk - 1.0) / tn);
+                const double tn = fista_tnext(tk);
+                const float beta = fista_beta(tk, tn);
                 tk = tn;
-                const bool mom = it > 0 && it + 1 < p.Nit;
+                const bool mom = fista_mom(it, p.Nit);
 #pragma unroll
                 for (int o = 0; o < NOWN; ++o) {
                     const int q = w + S * o;
                     const floatx4 xn = xbuf[q * 64 + lane];
-                    if (mom) xbuf[q * 64 + lane] = xn + beta * (xn - xold[o]);
+                    if (mom) xbuf[q * 64 + lane] = fista_extrapolate(xn, xold[o], beta);
                     xold[o] = xn;
                 }
             }
@@ -306,12 +293,7 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
         // ---- outputs: coefficients (owned tiles) and Phi = D x over this wave's row tiles ----------
         if (p.coefs && valid) {
             for (int q = w; q < NQ; q += S) {
-                const floatx4 xv = xbuf[q * 64 + lane];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int a = 16 * q + 4 * g + e;
-                    if (a < K) p.coefs[j * K + a] = xv[e];
-                }
+                ista_coefs4(p.coefs + j * K, 16 * q + 4 * g, K, xbuf[q * 64 + lane]);
             }
         }
         for (int t = t0; t < t1; ++t) {
@@ -322,10 +304,7 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
                     __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rDA, voff, (t * NQ + q) * 1024, 0));
                 const floatx4 xv = xbuf[q * 64 + lane];
                 floatx4 &acc = (q & 1) ? RB : RA;
-                acc = mfma16x16x4(a.x, xv[0], acc);
-                acc = mfma16x16x4(a.y, xv[1], acc);
-                acc = mfma16x16x4(a.z, xv[2], acc);
-                acc = mfma16x16x4(a.w, xv[3], acc);
+                acc = mfma_chain(acc, a, xv);
             }
             if (valid) {
                 const floatx4 R = RA + RB;
@@ -337,19 +316,11 @@ __global__ __launch_bounds__(64 * S, WPE) void k_ista_pat(IstaPatParams p) {
 
 // ---- host side --------------------------------------------------------------------------------
 
-// n_pad: the images' row count (the kernels index them with NT = n_pad / 16)
-static int64_t pat_images_floats(int64_t n_pad, int64_t K, int64_t npat) {
-    const int64_t NT = round_up(n_pad, 16) / 16, NQ = ista_nq(K);
-    return 2 * NT * NQ * 64 * 4 + npat * NQ * NQ * 256;
-}
-
 size_t ista_pat_workspace(int64_t n, int64_t K, int64_t npat) {
     if (n <= 0 || K <= 0 || K > 512 || npat <= 0) return 0;
-    return (size_t)pat_images_floats(n, K, npat) * sizeof(float);
+    return IstaImages(n, K, npat).bytes();
 }
 
-// Waves per workgroup: 8 for K > 128 (configs[2] sparse coding alone: 2.00 ms vs 2.10 ms with 4;
-// profiles/r04/ista_pat/), 4 below (one or two atom tiles per wave).
 template <int NQ, int S, bool ACCEL, int WPE = 2>
 static int launch_pat_k(const IstaPatParams &p, int64_t max_wg, hipStream_t st) {
     static std::atomic<uint64_t> opted{0};   // per device
@@ -365,22 +336,12 @@ static int launch_pat_k(const IstaPatParams &p, int64_t max_wg, hipStream_t st) 
 // set of patterns (the solver prepares at construction: both are fixed for a whole solve).
 int ista_pat_prepare(const float *D, int64_t n, int64_t K, const uint8_t *obs_pat, int64_t npat, int64_t n_pad,
                      void *ws, size_t ws_bytes, hipStream_t st) {
-    if (K < 1 || K > 512) return LRS_E_UNSUPPORTED;
-    // sized from n_pad, which sets the images' row count (lrs_ista_pat_workspace(n) covers the
-    // n_pad = round_up(n, 16) every caller of the solver uses; a larger n_pad needs its own size)
-    if (!ws || ws_bytes < (size_t)pat_images_floats(n_pad, K, npat) * sizeof(float)) return LRS_E_WORKSPACE;
-    const int NQ = ista_nq(K);
-    const int NT = (int)(n_pad / 16);
-    if ((int64_t)NT * NQ * 1024 >= ((int64_t)1 << 31)) return LRS_E_UNSUPPORTED;   // 32-bit buffer offsets
-    if (n > INT32_MAX / 2 || npat > 65535) return LRS_E_UNSUPPORTED;
-    float4 *DAf = reinterpret_cast<float4 *>(ws);
-    float4 *DTf = DAf + (size_t)NT * NQ * 64;
-    float4 *QAf = DTf + (size_t)NT * NQ * 64;
-    const int rc = ista_rs_images(D, n, K, NT, NQ, DAf, DTf, st);
-    if (rc) return rc;
-    const int NB = NQ / 4;
+    const IstaImages im(n_pad, K, npat);
+    if (const int rc = im.check(n, K, ws, ws_bytes, true)) return rc;
+    if (const int rc = ista_rs_images(D, n, K, im, ws, st)) return rc;
+    const int NQ = (int)im.NQ, NB = NQ / 4;
     hipLaunchKernelGGL(k_pat_gram, dim3((unsigned)(NB * (NB + 1) / 2), (unsigned)npat), dim3(256), 0, st, D, (int)n,
-                       (int)K, NQ, obs_pat, (int)n_pad, reinterpret_cast<float *>(QAf));
+                       (int)K, NQ, obs_pat, (int)n_pad, reinterpret_cast<float *>(im.QAf(ws)));
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
@@ -389,40 +350,18 @@ int ista_pat_launch(const float *Yb, const uint8_t *obs_pat, int64_t npat, const
                     int64_t n, int64_t n_pad, int64_t K, int64_t nb, const float *alpha, const double *thr, int Nit,
                     int prox, float *coefs, float *phi, void *ws, size_t ws_bytes, int64_t max_wg, hipStream_t st,
                     const float *x0, bool accel) {
-    if (K < 1 || K > 512) return LRS_E_UNSUPPORTED;
-    if (!ws || ws_bytes < (size_t)pat_images_floats(n_pad, K, npat) * sizeof(float)) return LRS_E_WORKSPACE;
-    const int NQ = ista_nq(K);
-    const int NT = (int)(n_pad / 16);
-    if ((int64_t)NT * NQ * 1024 >= ((int64_t)1 << 31)) return LRS_E_UNSUPPORTED;
-    if (n > INT32_MAX / 2 || npat > 65535) return LRS_E_UNSUPPORTED;
-    const float4 *DAf = reinterpret_cast<const float4 *>(ws);
-    const float4 *DTf = DAf + (size_t)NT * NQ * 64;
-    const float4 *QAf = DTf + (size_t)NT * NQ * 64;
+    const IstaImages im(n_pad, K, npat);
+    if (const int rc = im.check(n, K, ws, ws_bytes, true)) return rc;
     if (ntiles == 0) return LRS_OK;
-    IstaPatParams p{Yb, obs_pat, plan, DAf, DTf, QAf, alpha, thr, coefs, phi, x0, (int)n_pad, (int)K, Nit, prox,
-                    nb, ntiles, npat, 7.0};
-    const int waves = NQ >= 16 ? 8 : 4;
-    if (accel) {
-        switch (NQ) {
-        case 4: return launch_pat_k<4, 4, true>(p, max_wg, st);
-        case 8: return launch_pat_k<8, 4, true>(p, max_wg, st);
-        case 16: return launch_pat_k<16, 8, true>(p, max_wg, st);
-        default: return launch_pat_k<32, 8, true>(p, max_wg, st);
-        }
-    }
-    switch (NQ) {
-    case 4: return launch_pat_k<4, 4, false>(p, max_wg, st);
-    case 8: return launch_pat_k<8, 4, false>(p, max_wg, st);
-    case 16:
-        // 8 waves, registers unbounded (192, one workgroup per CU).  The 128-register bound (two
-        // workgroups per CU; WPE = 4) is bit-identical and a little faster
-        // (configs[3]'s sparse coding 11.3 -> 10.6 ms, configs[2]'s beside the DIP 1.745 -> 1.683 ms;
-        // the configs[2] bench 7.87 either way, profiles/r04/ista_pat_wpe/), but spills 37 registers
-        // (152 B of scratch per lane, 29 with a 2-deep ring): the PMC pass then measured 1.26 GB of
-        // fabric traffic per configs[2] launch instead of 122 MB (profiles/r04/ista_pat_spill/).
-        return waves == 8 ? launch_pat_k<16, 8, false>(p, max_wg, st) : launch_pat_k<16, 4, false>(p, max_wg, st);
-    default: return launch_pat_k<32, 8, false>(p, max_wg, st);
-    }
+    IstaPatParams p{Yb, obs_pat, plan, im.DAf(ws), im.DTf(ws), im.QAf(ws), alpha, thr, coefs, phi, x0, (int)n_pad,
+                    (int)K, Nit, prox, nb, ntiles, npat, 7.0};
+    // Waves per workgroup: 8 for K > 128 (configs[2] sparse coding alone: 2.00 ms vs 2.10 ms with 4;
+    // profiles/r04/ista_pat/), 4 below (one or two atom tiles per wave).  Registers bounded for WPE = 2
+    // (DESIGN §4 has the measurement of WPE = 4).
+    return ista_dispatch_nq((int)im.NQ, accel, [&](auto nq, auto acc) {
+        constexpr int NQ = decltype(nq)::value;
+        return launch_pat_k<NQ, (NQ >= 16 ? 8 : 4), decltype(acc)::value>(p, max_wg, st);
+    });
 }
 
 }  // namespace lrs

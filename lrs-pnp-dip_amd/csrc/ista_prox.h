@@ -1,6 +1,9 @@
 // The ISTA prox of one gradient row in LDS, shared by the row-split (ista_rs.hip) and per-pattern
 // Gram (ista_pat.hip) kernels: the skimage fast NLM chunk, the MATLAB NLmeansfilter point, the
-// soft threshold's quotient, and the LDS row swizzle both kernels use.
+// soft threshold's quotient and the LDS row swizzle both kernels use; and the arithmetic of the stages the two
+// kernels have in common, as pure functions of values: the 4-MFMA chain, the FISTA rule, the gradient row,
+// the coefs write, the image resource.  Loops, LDS and global addressing and barriers stay in the kernels.
+// profiles/ista_stages/notes.txt records, form by form, which of these left every kernel's code as it was.
 #pragma once
 #include "lrs_common.h"
 #include "lrs_nlm.h"
@@ -100,12 +103,57 @@ __device__ __forceinline__ void nlm_matlab_krow_d(double (&krow)[7]) {
     }
 }
 
+// acc + sum_e a[e] r[e] on v_mfma_f32_16x16x4_f32, e in order (r: float[4] or floatx4 in registers): b, D x
+// and Q x in both kernels and k_ista_pat's Phi.  Not through it: k_ista_rs's D^T r (two chains interleaved
+// pairwise in row_tile) and its Phi epilogue (written out there)
+template <class R>
+__device__ __forceinline__ floatx4 mfma_chain(floatx4 acc, float4 a, const R &r) {
+    acc = mfma16x16x4(a.x, r[0], acc);
+    acc = mfma16x16x4(a.y, r[1], acc);
+    acc = mfma16x16x4(a.z, r[2], acc);
+    acc = mfma16x16x4(a.w, r[3], acc);
+    return acc;
+}
+
+// FISTA (lrs_ista_opts.accel), the rule both kernels follow, wave-uniform:
+//   t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2 in fp64, beta_k = (t_k - 1) / t_{k+1} rounded once to float32,
+//   and iteration `it` of Nit extrapolates unless it is the first (beta_1 = 0, so x_{k-1} needs no start
+//   value) or the last (which leaves x_Nit itself for the outputs).
+__device__ __forceinline__ double fista_tnext(double tk) { return 0.5 * (1.0 + sqrt(1.0 + 4.0 * tk * tk)); }
+__device__ __forceinline__ float fista_beta(double tk, double tn) { return (float)((tk - 1.0) / tn); }
+__device__ __forceinline__ bool fista_mom(int it, int Nit) { return it > 0 && it + 1 < Nit; }
+
+// z_{k+1} = x_k + beta (x_k - x_{k-1}) of one atom tile
+__device__ __forceinline__ floatx4 fista_extrapolate(floatx4 xn, floatx4 xold, float beta) { return xn + beta * (xn - xold); }
+
 // a / b from y = 1/b (correctly rounded reciprocal) and one remainder step: the IEEE quotient
 // away from overflow / underflow (…1-LiP.py:190 torch division by alpha)
 __device__ __forceinline__ float rs_div(float a, float b, float y) {
     const float q = a * y;
     const float r = __fmaf_rn(-b, q, a);
     return __fmaf_rn(r, y, q);
+}
+
+// g = x + num / alpha of one atom tile: the lane's 4 atoms of its gradient row
+__device__ __forceinline__ float4 ista_grad4(floatx4 xo, floatx4 num, float al, float ral) {
+    float4 gr;
+    gr.x = xo[0] + rs_div(num[0], al, ral);
+    gr.y = xo[1] + rs_div(num[1], al, ral);
+    gr.z = xo[2] + rs_div(num[2], al, ral);
+    gr.w = xo[3] + rs_div(num[3], al, ral);
+    return gr;
+}
+
+// atoms a0 .. a0 + 3 (below K) of one block's coefficient row
+__device__ __forceinline__ void ista_coefs4(float *row, int a0, int K, floatx4 xv) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (a0 + e < K) row[a0 + e] = xv[e];
+}
+
+// A fragment-ordered image of `bytes` bytes as a buffer resource (raw loads, bounds-checked against bytes)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ista_image(const float4 *img, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, bytes, 0x00020000);
 }
 
 }  // namespace lrs

@@ -124,8 +124,8 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
     // fragment k of row tile t: k < NQ -> DAf q = k, else DTf q = k - NQ.  Buffer loads: the lane's
     // 16-byte offset is the only VGPR, the wave-uniform fragment offset goes in soffset.
     const int img_bytes = NT * NQ * 1024;
-    const __amdgpu_buffer_rsrc_t rDA = __builtin_amdgcn_make_buffer_rsrc((void *)p.DAf, 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rDT = __builtin_amdgcn_make_buffer_rsrc((void *)p.DTf, 0, img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rDA = ista_image(p.DAf, img_bytes);
+    const __amdgpu_buffer_rsrc_t rDT = ista_image(p.DTf, img_bytes);
     const int voff = lane * 16;
     auto frag = [&](int t, int k) -> float4 {
         const auto v = k < NQ ? __builtin_amdgcn_raw_buffer_load_b128(rDA, voff, (t * NQ + k) * 1024, 0)
@@ -138,14 +138,6 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) bits |= (((mv >> (8 * e)) & 0xffu) ? 1u : 0u) << e;
         return bits;
-    };
-    auto gq = [&](const floatx4 &G, float4 a, const float (&r)[4]) -> floatx4 {
-        floatx4 acc = G;
-        acc = mfma16x16x4(a.x, r[0], acc);
-        acc = mfma16x16x4(a.y, r[1], acc);
-        acc = mfma16x16x4(a.z, r[2], acc);
-        acc = mfma16x16x4(a.w, r[3], acc);
-        return acc;
     };
 
     // mask bits of this wave's row tiles (tile i: word i / 8, bits 4 (i % 8) .. +3); tiles beyond
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
         const float r[4] = {(m4 & 1u) ? yv.x : 0.f, (m4 & 2u) ? yv.y : 0.f, (m4 & 4u) ? yv.z : 0.f,
                             (m4 & 8u) ? yv.w : 0.f};
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) G[q] = gq(G[q], frag(t, NQ + q), r);
+        for (int q = 0; q < NQ; ++q) G[q] = mfma_chain(G[q], frag(t, NQ + q), r);
     }
     auto publish = [&]() {          // partials of the tiles this wave does not own
         if (S > 1) {
@@ -217,10 +209,7 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
             if (k < NQ) {
                 const floatx4 xv = xbuf[k * 64 + lane];
                 floatx4 &acc = (k & 1) ? RB : RA;      // even / odd q on two accumulators (MFMA latency)
-                acc = mfma16x16x4(a.x, xv[0], acc);
-                acc = mfma16x16x4(a.y, xv[1], acc);
-                acc = mfma16x16x4(a.z, xv[2], acc);
-                acc = mfma16x16x4(a.w, xv[3], acc);
+                acc = mfma_chain(acc, a, xv);
                 if (k == NQ - 1) {
                     const floatx4 R = RA + RB;
 #pragma unroll
@@ -262,13 +251,8 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
         for (int q = 0; q < NQ; ++q) {
             if (w == q % S) {
                 const floatx4 sum = reduced(q, bown[q / S]);
-                const floatx4 xo = xbuf[q * 64 + lane];
-                float4 gr;
-                gr.x = xo[0] + rs_div(sum[0], al, ral);
-                gr.y = xo[1] + rs_div(sum[1], al, ral);
-                gr.z = xo[2] + rs_div(sum[2], al, ral);
-                gr.w = xo[3] + rs_div(sum[3], al, ral);
-                *reinterpret_cast<float4 *>(&gbuf[jl * KP + gsw(jl, 16 * q + 4 * g)]) = gr;
+                *reinterpret_cast<float4 *>(&gbuf[jl * KP + gsw(jl, 16 * q + 4 * g)]) =
+                    ista_grad4(xbuf[q * 64 + lane], sum, al, ral);
             }
         }
         __syncthreads();
@@ -299,15 +283,15 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
         }
         if constexpr (ACCEL) {
             // ---- momentum on the owned tiles: xbuf <- z_{k+1}, but x_Nit itself after the last prox ----
-            const double tn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * tk * tk));
-            const float beta = (float)((tk - 1.0) / tn);
+            const double tn = fista_tnext(tk);
+            const float beta = fista_beta(tk, tn);
             tk = tn;
-            const bool mom = it > 0 && it + 1 < p.Nit;
+            const bool mom = fista_mom(it, p.Nit);
             if constexpr (XOLD_LDS) {
 #pragma unroll 1
                 for (int q = 0; q < NQ; ++q) {
                     const floatx4 xn = xbuf[q * 64 + lane];
-                    if (mom) xbuf[q * 64 + lane] = xn + beta * (xn - xoldl[q * 64 + lane]);
+                    if (mom) xbuf[q * 64 + lane] = fista_extrapolate(xn, xoldl[q * 64 + lane], beta);
                     xoldl[q * 64 + lane] = xn;
                 }
             } else {
@@ -315,7 +299,7 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
                 for (int q = 0; q < NQ; ++q) {
                     if (w == q % S) {
                         const floatx4 xn = xbuf[q * 64 + lane];
-                        if (mom) xbuf[q * 64 + lane] = xn + beta * (xn - xold[q / S]);
+                        if (mom) xbuf[q * 64 + lane] = fista_extrapolate(xn, xold[q / S], beta);
                         xold[q / S] = xn;
                     }
                 }
@@ -327,12 +311,7 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
     // ---- outputs: coefficients (owned tiles) and Phi = D x over this wave's row tiles ----------
     if (p.coefs && valid) {
         for (int q = w; q < NQ; q += S) {
-            const floatx4 xv = xbuf[q * 64 + lane];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int a = 16 * q + 4 * g + e;
-                if (a < K) p.coefs[j * K + a] = xv[e];
-            }
+            ista_coefs4(p.coefs + j * K, 16 * q + 4 * g, K, xbuf[q * 64 + lane]);
         }
     }
     for (int t = t0; t < t1; ++t) {
@@ -342,6 +321,7 @@ __global__ __launch_bounds__(256, MINW) void k_ista_rs(IstaRsParams p) {
             const float4 a = frag(t, q);
             const floatx4 xv = xbuf[q * 64 + lane];
             floatx4 &acc = (q & 1) ? RB : RA;
+            // mfma_chain(acc, a, xv), written out: through the function the operands of RA + RB swap in 13 forms
             acc = mfma16x16x4(a.x, xv[0], acc);
             acc = mfma16x16x4(a.y, xv[1], acc);
             acc = mfma16x16x4(a.z, xv[2], acc);
@@ -406,10 +386,7 @@ static int cu_count() {
     return g_cu_count;
 }
 
-size_t ista_rs_workspace(int64_t n, int64_t K) {
-    const int64_t n_pad = round_up(n, 16);
-    return (size_t)2 * n_pad * ista_nq(K) * 16 * sizeof(float);
-}
+size_t ista_rs_workspace(int64_t n, int64_t K) { return IstaImages(n, K).bytes(); }
 
 // Waves per workgroup S: the per-SIMD makespan ceil(tiles S / SIMDs) / S, smallest S on ties;
 // capped by the rows (one row tile per wave at least) and by LDS (two workgroups per CU at MINW 2);
@@ -458,10 +435,11 @@ static int launch_rs(const IstaRsParams &p, int NT, int64_t max_wg, hipStream_t 
 }
 
 // the two fragment-ordered dictionary images (also used by the per-pattern Gram kernel, ista_pat.hip)
-int ista_rs_images(const float *D, int64_t n, int64_t K, int NT, int NQ, float4 *DAf, float4 *DTf, hipStream_t st) {
-    const int64_t total = (int64_t)NT * NQ * 64;
+int ista_rs_images(const float *D, int64_t n, int64_t K, const IstaImages &im, void *ws, hipStream_t st) {
+    const int64_t total = im.d_float4();
     const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_ista_rs_prep, dim3(blocks), dim3(256), 0, st, D, (int)n, (int)K, NT, NQ, DAf, DTf);
+    hipLaunchKernelGGL(k_ista_rs_prep, dim3(blocks), dim3(256), 0, st, D, (int)n, (int)K, (int)im.NT, (int)im.NQ,
+                       im.DAf(ws), im.DTf(ws));
     LRS_CHECK_LAUNCH();
     return LRS_OK;
 }
@@ -469,32 +447,13 @@ int ista_rs_images(const float *D, int64_t n, int64_t K, int NT, int NQ, float4 
 int ista_rs_launch(const float *Yb, const uint8_t *obs, const float *D, int64_t n, int64_t n_pad, int64_t K, int64_t nb,
                    const float *alpha, const double *thr, int Nit, int prox, float *coefs, float *phi, void *ws,
                    size_t ws_bytes, int64_t max_wg, hipStream_t st, const float *x0, bool accel) {
-    if (K < 1 || K > 512) return LRS_E_UNSUPPORTED;
-    const int NQ = ista_nq(K);
-    const int NT = (int)(n_pad / 16);
-    // the dictionary images are addressed by 32-bit buffer offsets (t * NQ + k) * 1024
-    if ((int64_t)NT * NQ * 1024 >= ((int64_t)1 << 31)) return LRS_E_UNSUPPORTED;
-    // the images have NT = n_pad / 16 row tiles: size the check from n_pad (ista_rs_workspace(n)
-    // covers n_pad = round_up(n, 16); a larger n_pad needs lrs_ista_workspace(n_pad, ...))
-    if (!ws || ws_bytes < ista_rs_workspace(n_pad, K)) return LRS_E_WORKSPACE;
-    float4 *DAf = reinterpret_cast<float4 *>(ws);
-    float4 *DTf = DAf + (size_t)NT * NQ * 64;
-    if (const int rc = ista_rs_images(D, n, K, NT, NQ, DAf, DTf, st)) return rc;
-    IstaRsParams p{Yb, obs, DAf, DTf, alpha, thr, coefs, phi, (int)n_pad, (int)K, Nit, prox, nb, 7.0, x0};
-    if (accel) {
-        switch (NQ) {
-        case 4: return launch_rs<4, true>(p, NT, max_wg, st);
-        case 8: return launch_rs<8, true>(p, NT, max_wg, st);
-        case 16: return launch_rs<16, true>(p, NT, max_wg, st);
-        default: return launch_rs<32, true>(p, NT, max_wg, st);
-        }
-    }
-    switch (NQ) {
-    case 4: return launch_rs<4, false>(p, NT, max_wg, st);
-    case 8: return launch_rs<8, false>(p, NT, max_wg, st);
-    case 16: return launch_rs<16, false>(p, NT, max_wg, st);
-    default: return launch_rs<32, false>(p, NT, max_wg, st);
-    }
+    const IstaImages im(n_pad, K);
+    if (const int rc = im.check(n, K, ws, ws_bytes, false)) return rc;
+    if (const int rc = ista_rs_images(D, n, K, im, ws, st)) return rc;
+    IstaRsParams p{Yb, obs, im.DAf(ws), im.DTf(ws), alpha, thr, coefs, phi, (int)n_pad, (int)K, Nit, prox, nb, 7.0, x0};
+    return ista_dispatch_nq((int)im.NQ, accel, [&](auto nq, auto acc) {
+        return launch_rs<decltype(nq)::value, decltype(acc)::value>(p, (int)im.NT, max_wg, st);
+    });
 }
 
 int nlm_matlab_col_launch(const float *g, int64_t ldg, float *out, int64_t ldo, int64_t K, int64_t nvec, double h,
