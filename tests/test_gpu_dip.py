@@ -959,3 +959,27 @@ def test_mssim_matches_torch_restatement(L):
     got = mssim(a.cuda(), b.cuda())
     assert abs(got - float(ref)) < 1e-5
     assert abs(mssim(a.cuda(), a.cuda()) - 1.0) < 1e-6
+
+
+@pytest.mark.parametrize("C,H,W", [(3, 4, 13), (40, 232, 232)])
+def test_mssim_small_and_large_images(L, C, H, W):
+    """lrs_ssim_f32 on images smaller than the 11 x 11 window (every window hangs over the zero border)
+    and on C H W = 2152960 > 8192 * 256 elements, against the fp64 restatement and at the 1e-5 of
+    test_mssim_matches_torch_restatement."""
+    import math
+    from lrspnp.metrics import mssim
+    g = torch.Generator().manual_seed(C)
+    a = torch.rand(C, H, W, generator=g)
+    b = (a + 0.1 * torch.randn(C, H, W, generator=g)).clamp(0, 1)
+    gauss = torch.tensor([math.exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)])
+    gauss = gauss / gauss.sum()
+    win = (gauss[:, None] @ gauss[None, :]).double().expand(C, 1, 11, 11)
+    A, Bt = a.double()[None], b.double()[None]
+    conv = lambda t: F.conv2d(t, win, padding=5, groups=C)
+    mu1, mu2 = conv(A), conv(Bt)
+    s1, s2, s12 = conv(A * A) - mu1 ** 2, conv(Bt * Bt) - mu2 ** 2, conv(A * Bt) - mu1 * mu2
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    ref = (((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 ** 2 + mu2 ** 2 + C1) * (s1 + s2 + C2))).mean()
+    got = mssim(a.cuda(), b.cuda())
+    assert abs(got - float(ref)) < 1e-5, (got, float(ref))
+    assert abs(mssim(a.cuda(), a.cuda()) - 1.0) < 1e-6

@@ -528,6 +528,135 @@ def test_admm_update_bitexact_vs_oracle(ops):
         assert np.allclose(norms.cpu().numpy(), nref, rtol=1e-10)
 
 
+def _admm_case(ops, P, B, bb, sliding, seed, want_norms=True, want_imout=True):
+    """One lrs_admm_update_f32 call on the grid (P, B, bb, sliding) next to oracle_admm_update on the
+    same corner list.  Returns the kernel's (X, L1, L2, imout, norms), the oracle's (X, L1, L2, imout)
+    and the inputs (X, L1, L2)."""
+    import ctypes
+    rng = np.random.default_rng(seed)
+    rows, cols = O.block_grid(P, B, bb, sliding)
+    nb, n = rows.size, bb * bb
+    n_pad = -(-n // 16) * 16
+    mk = lambda *s: rng.standard_normal(s).astype(np.float32)
+    Y, U, L1, L2, X = mk(P, B), mk(P, B), mk(P, B), mk(P, B), mk(P, B)
+    M = (rng.random((P, B)) > 0.1).astype(np.float32)
+    PHI = mk(nb, n)
+    Xo, L1o, L2o, IMo = (np.empty_like(X) for _ in range(4))
+    O.lib().oracle_admm_update(P, B, bb, nb, rows, cols, PHI, Y, M, U, L1, L2, 0.5, np.float32(0.15),
+                               np.float32(0.9), Xo, L1o, L2o, IMo.ctypes.data_as(ctypes.c_void_p), None)
+    r, c = ops.block_grid(P, B, bb, sliding)
+    assert np.array_equal(r, rows) and np.array_equal(c, cols)
+    rs, cs = np.unique(r), np.unique(c)
+    rlo, rhi = ops.cover_ranges(P, bb, rs)
+    clo, chi = ops.cover_ranges(B, bb, cs)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    grid = dict(rstarts=d(rs), cstarts=d(cs), nbr=rs.size, rlo=d(rlo), rhi=d(rhi), clo=d(clo), chi=d(chi))
+    Xd, L1d, L2d = d(X), d(L1), d(L2)
+    im = torch.full_like(Xd, 7.0) if want_imout else None
+    norms = torch.full((3,), 7.0, dtype=torch.float64, device="cuda") if want_norms else None
+    ops.admm_update(Xd, L1d, L2d, d(Y), d(M), d(U), d(np.pad(PHI, ((0, 0), (0, n_pad - n)))), bb, grid,
+                    np.float32(0.5), np.float32(0.15), np.float32(0.9), norms=norms, imout=im)
+    got = (Xd.cpu().numpy(), L1d.cpu().numpy(), L2d.cpu().numpy(), im.cpu().numpy() if want_imout else None,
+           norms.cpu().numpy() if want_norms else None)
+    return got, (Xo, L1o, L2o, IMo), (X, L1, L2)
+
+
+def _admm_check(got, ref, inp):
+    bits = lambda a: a.view(np.uint32)
+    for g, r in zip(got[:3], ref[:3]):
+        assert np.array_equal(bits(g), bits(r))
+    if got[3] is not None:
+        assert np.array_equal(bits(got[3]), bits(ref[3]))
+    if got[4] is not None:
+        # the atomics leave the order of the fp64 sums free: not bit-exact
+        nref = [np.sum((r.astype(np.float64) - x) ** 2) for r, x in zip(ref[:3], inp)]
+        assert np.allclose(got[4], nref, rtol=1e-10, atol=0.0)
+
+
+@pytest.mark.parametrize("P,B,bb,sliding", [(40, 33, 8, 3), (20 * 20, 24, 8, 4), (50, 50, 8, 1),
+                                            (1100, 500, 36, 36)])
+def test_admm_update_overlapping_covers_bitexact(ops, P, B, bb, sliding):
+    """The gather over overlapping covers (sliding < bb: up to bb^2 blocks per element, walked in the
+    reference's block order), and P * B = 550000 > 2048 * 256 threads, where every thread takes a second
+    element of the grid-stride loop."""
+    _admm_check(*_admm_case(ops, P, B, bb, sliding, seed=P + sliding))
+
+
+@pytest.mark.parametrize("want_norms,want_imout", [(False, True), (True, False), (False, False)])
+def test_admm_update_optional_outputs(ops, want_norms, want_imout):
+    """norms = NULL and imout = NULL: X, L1 and L2 keep the bits of the full call."""
+    full = _admm_case(ops, 40, 33, 8, 3, seed=21)
+    part = _admm_case(ops, 40, 33, 8, 3, seed=21, want_norms=want_norms, want_imout=want_imout)
+    _admm_check(*full)
+    _admm_check(*part)
+    for a, b in zip(full[0][:3], part[0][:3]):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def test_cover_ranges_refusal_and_gap(ops):
+    from lrspnp._lib import LrsError
+    for starts in ([0, 4, 4, 8], [0, 8, 4]):
+        with pytest.raises(LrsError, match="LRS_E_INVALID"):
+            ops.cover_ranges(12, 4, np.array(starts, np.int32))
+    lo, hi = ops.cover_ranges(14, 4, np.array([0, 10], np.int32))       # nothing covers 4..9
+    covered = np.array([x < 4 or x >= 10 for x in range(14)])
+    assert np.all(hi[~covered] < lo[~covered])
+    assert np.all(lo[:4] == 0) and np.all(hi[:4] == 0) and np.all(lo[10:] == 1) and np.all(hi[10:] == 1)
+
+
+def _im2col_case(ops, P, B, bb, sliding, n_pad, with_L, seed):
+    rng = np.random.default_rng(seed)
+    mu = np.float32(0.15)
+    X = rng.standard_normal((P, B)).astype(np.float32)
+    Lm = rng.standard_normal((P, B)).astype(np.float32) if with_L else None
+    # an element that cancels to 0 (X + L/mu = 1 - mu/mu), a -0.0 and a +0.0: all unobserved.  (0, 0) and
+    # (1, 2) lie in the first block of every grid; with sliding < bb the last rows may be in no block
+    X[0, 0] = 1.0
+    X[1, 2] = -0.0
+    X[P // 2, B // 2] = 0.0
+    if with_L:
+        Lm[0, 0] = -mu
+        Lm[1, 2] = -0.0
+        Lm[P // 2, B // 2] = 0.0
+    else:
+        X[0, 0] = 0.0
+    Z = X + Lm / mu if with_L else X
+    assert Z.dtype == np.float32 and Z[0, 0] == 0.0 and np.signbit(Z[1, 2])
+    rows, cols = O.block_grid(P, B, bb, sliding)
+    ref = O.im2col(Z, bb, rows, cols)
+    r, c = ops.block_grid(P, B, bb, sliding)
+    assert np.array_equal(r, rows) and np.array_equal(c, cols)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    nb, n = rows.size, bb * bb
+    Yb = torch.full((nb, n_pad), 7.0, dtype=torch.float32, device="cuda")        # the padding must be written
+    obs = torch.full((nb, n_pad), 255, dtype=torch.uint8, device="cuda")
+    ops.im2col(d(X), d(Lm) if with_L else None, mu, bb, d(r), d(c), n_pad, Yb=Yb, obs=obs, want_obs=True)
+    Yb, obs = Yb.cpu().numpy(), obs.cpu().numpy()
+    assert np.array_equal(Yb[:, :n].view(np.uint32), ref.view(np.uint32))
+    assert not Yb[:, n:].view(np.uint32).any()                                   # exactly +0.0
+    assert np.array_equal(obs[:, :n], (ref != 0).astype(np.uint8))
+    assert not obs[:, n:].any()
+    assert (ref == 0).sum() >= 3 and np.signbit(ref[ref == 0]).any()
+    Yb2 = ops.im2col(d(X), d(Lm) if with_L else None, mu, bb, d(r), d(c), n_pad).cpu().numpy()   # obs = NULL
+    assert np.array_equal(Yb2.view(np.uint32), Yb.view(np.uint32))
+
+
+@pytest.mark.parametrize("with_L", [True, False])
+@pytest.mark.parametrize("extra_pad", [0, 16])
+@pytest.mark.parametrize("P,B,bb,sliding", [(103, 29, 7, 7), (40, 33, 8, 3), (9, 9, 9, 1)])
+def test_im2col_bitexact_vs_oracle(ops, P, B, bb, sliding, extra_pad, with_L):
+    """lrs_im2col_f32 alone: block vectors of X + L/mu in float32, bit for bit; the padding columns
+    exactly 0; obs 1 exactly where the value is non-zero."""
+    n_pad = -(-bb * bb // 16) * 16 + extra_pad
+    _im2col_case(ops, P, B, bb, sliding, n_pad, with_L, seed=P)
+
+
+def test_im2col_grid_stride_wrap(ops):
+    """nb * n_pad = 249001 * 80 > 65536 * 256: the grid-stride loop's second trip."""
+    assert O.block_grid(1500, 1500, 8, 3)[0].size * 80 > 65536 * 256
+    _im2col_case(ops, 1500, 1500, 8, 3, 80, True, seed=1500)
+
+
 def test_ista_both_product_precisions_match_oracle():
     """The resident kernel's products in exact f32 MFMA and in split-bf16 MFMA (the default):
     both within 1e-5 of the oracle, and within 1e-6 of each other."""
@@ -643,3 +772,19 @@ def test_psnr_bands_kernel_vs_oracle():
     assert got[5] == 100.0
     mask = np.arange(B) != 5
     np.testing.assert_allclose(got[mask], ref[mask], rtol=1e-6)
+
+
+@pytest.mark.parametrize("B,H,W", [(300, 29, 31), (37, 10, 10)])
+def test_psnr_bands_wide_and_short(B, H, W):
+    """lrs_psnr_bands_f32 with more bands than a workgroup has threads (B = 300) and with fewer rows
+    than row slabs (P = 100), at the tolerance of test_psnr_bands_kernel_vs_oracle."""
+    from lrspnp.metrics import psnr_bands
+    rng = np.random.default_rng(B)
+    clean = rng.random((B, H, W)).astype(np.float32)
+    noisy = (clean + 0.05 * rng.standard_normal((B, H, W))).astype(np.float32)
+    noisy[B - 1] = clean[B - 1]
+    X = np.ascontiguousarray(noisy.transpose(2, 1, 0).reshape(H * W, B))
+    got = psnr_bands(torch.from_numpy(X).cuda(), torch.from_numpy(clean).cuda()).cpu().numpy()
+    ref = O.psnr_bands(X, clean)
+    assert got.shape == (B,) and got[B - 1] == 100.0
+    np.testing.assert_allclose(got[:B - 1], ref[:B - 1], rtol=1e-6)
