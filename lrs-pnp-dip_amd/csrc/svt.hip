@@ -15,15 +15,14 @@
 //      Z V diag((s-tau)_+/s) V^T == U_s (S-tau)_+ V_h, and E is small so its f32 rounding costs
 //      << 1e-6 relative in U.
 // The whole chain runs on its own stream beside the sparse-coding kernel.
-// Wide cubes (256 < B <= 512, svt_wide.h): 1 and 5 are tiled over column panels, and 2-4 run on the
-// packed triangle in the workspace whatever solver the caller asked for, unless LRS_SVT_WIDE_TRI asks
-// for 3' over many workgroups with its certificate as GEMMs on the fp64 matrix cores (svt_wide_eig.h);
-// LRS_SVT_WIDE_MW beside it spreads that chain's Householder reduction over many workgroups too, one
-// launch per column (svt_wide_mw.h).
+// Wide cubes (256 < B <= 512, svt_wide.h): 1 and 5 are tiled over column panels, and 2-4 run on the packed
+// triangle in the workspace, or 3' over many workgroups with its certificate as GEMMs on the fp64 matrix cores
+// (svt_wide_eig.h), its Householder reduction in one workgroup or one launch per column (svt_wide_mw.h).
 //
 // The stages: svt_gram.h (1, 2), svt_jacobi.h (3, 4), svt_eig.h (3'), svt_apply.h (5), svt_wide.h (the
 // wide Gram), svt_wide_eig.h (the wide 3'), svt_wide_mw.h (its many-workgroup reduction); svt_ws.h has
-// the workspace and the table of which form serves which band count.  Here: the launchers and the C entry points.
+// the workspace and the table of which form serves which band count.  Here: svt_plan (which chain a flag
+// word asks for at a band count, decided once per call), one launcher per chain, and the C entry points.
 #include <algorithm>
 
 #include "lrs_common.h"
@@ -76,23 +75,39 @@ extern "C" size_t lrs_svt_workspace(int64_t P, int64_t B) {
 
 extern "C" int64_t lrs_svt_max_bands(void) { return kWideMaxBp; }
 
-// Above kMaxBp the wide-band path serves, up to kWideMaxBp; it has no multi-workgroup solver.
-static int svt_shape_check(int64_t B, int warm) {
-    const int64_t Bp = B + (B & 1);
-    if (Bp > kWideMaxBp) return LRS_E_UNSUPPORTED;
-    if (Bp > kMaxBp && (warm & LRS_SVT_MULTI_WG)) return LRS_E_UNSUPPORTED;
-    return LRS_OK;
-}
+// One call's chain, resolved once from (B, flags): the entry points read this and nothing else about the flag
+// word.  Bp is B rounded up to even.
+//   Bp > 512 (kWideMaxBp), or Bp > 256 (kMaxBp) with LRS_SVT_MULTI_WG: LRS_E_UNSUPPORTED.
+//   Bp <= 256: LRS_SVT_WIDE_TRI and LRS_SVT_WIDE_MW are ignored.  LRS_SVT_JACOBI: the Jacobi chain; otherwise
+//     LRS_SVT_MULTI_WG: the tridiagonal chain over many workgroups; otherwise that chain in one workgroup.
+//   Bp > 256: LRS_SVT_WIDE_TRI without LRS_SVT_JACOBI: the wide tridiagonal chain, its Householder reduction over
+//     many workgroups with LRS_SVT_WIDE_MW (mw_reduction); otherwise the wide Jacobi chain, LRS_SVT_WIDE_MW ignored.
+//   warm: LRS_SVT_WARM.  warm_products (_gram forms A0 = V^T G V): warm, on a Jacobi chain, narrow or wide.
+//   reset_state (_gram zeroes the state words): the flag word is zero once the ignored bits are dropped, or the
+//     chain is the wide tridiagonal one and LRS_SVT_WARM is clear.  So a cold LRS_SVT_JACOBI or LRS_SVT_MULTI_WG
+//     call at Bp <= 256 keeps the words of the call before it, which is harmless: k_jacobi_lds ignores V when
+//     its warm argument is 0, and the tridiagonal chains rewrite words 0, 1 and 4.
+enum SvtChain { kSvtTri = 0, kSvtTriMw = 1, kSvtJacobi = 2, kSvtWideJacobi = 3, kSvtWideTri = 4 };
+struct SvtPlan {
+    int rc, warm;   // rc: LRS_OK or LRS_E_UNSUPPORTED (the other fields are then unset)
+    SvtChain chain;
+    bool mw_reduction, reset_state, warm_products;
+};
 
-// The wide tridiagonal chain (svt_wide_eig.h) serves; an explicit LRS_SVT_JACOBI wins.
-static bool svt_wide_tri(int64_t B, int warm) {
-    return svt_shape(B).wide && (warm & LRS_SVT_WIDE_TRI) && !(warm & LRS_SVT_JACOBI);
-}
-// The flag word as the launchers read it: LRS_SVT_WIDE_TRI means something above kMaxBp only, and
-// LRS_SVT_WIDE_MW only where the wide tridiagonal chain serves.
-static int svt_flags(int64_t B, int warm) {
-    if (!svt_shape(B).wide) warm &= ~LRS_SVT_WIDE_TRI;
-    return svt_wide_tri(B, warm) ? warm : warm & ~LRS_SVT_WIDE_MW;
+static SvtPlan svt_plan(int64_t B, int flags) {
+    SvtPlan p{};
+    const int64_t Bp = B + (B & 1);
+    const bool wide = Bp > kMaxBp, jacobi = flags & LRS_SVT_JACOBI;
+    p.rc = Bp > kWideMaxBp || (wide && (flags & LRS_SVT_MULTI_WG)) ? LRS_E_UNSUPPORTED : LRS_OK;
+    if (p.rc != LRS_OK) return p;
+    p.chain = wide ? ((flags & LRS_SVT_WIDE_TRI) && !jacobi ? kSvtWideTri : kSvtWideJacobi)
+                   : jacobi ? kSvtJacobi : (flags & LRS_SVT_MULTI_WG) ? kSvtTriMw : kSvtTri;
+    const bool wide_tri = p.chain == kSvtWideTri;
+    p.warm = flags & LRS_SVT_WARM;
+    p.mw_reduction = wide_tri && (flags & LRS_SVT_WIDE_MW);
+    p.warm_products = p.warm && (p.chain == kSvtJacobi || p.chain == kSvtWideJacobi);
+    p.reset_state = wide_tri ? !p.warm : !(flags & ~(LRS_SVT_WIDE_TRI | LRS_SVT_WIDE_MW));
+    return p;
 }
 
 extern "C" int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, int64_t *ld) {
@@ -107,13 +122,12 @@ extern "C" int lrs_svt_gram_offset(int64_t P, int64_t B, int64_t *offset_bytes, 
 extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64_t P, int64_t B, int warm, void *ws,
                                 size_t ws_bytes, void *stream) {
     if (!X || !ws || P <= 0 || B <= 0) return LRS_E_INVALID;
-    if (svt_shape_check(B, warm) != LRS_OK) return LRS_E_UNSUPPORTED;
+    const SvtPlan plan = svt_plan(B, warm);
+    if (plan.rc != LRS_OK) return plan.rc;
     if (ws_bytes < svt_ws_offsets(B).total) return LRS_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     SvtWs w = svt_ws_layout(ws, B);
-    const bool wide_tri = svt_wide_tri(B, warm);
-    warm = svt_flags(B, warm);
-    if (!warm || (wide_tri && !(warm & LRS_SVT_WARM))) {
+    if (plan.reset_state) {
         hipError_t e = hipMemsetAsync(w.state, 0, sizeof(int) * 8, st);   // words 0-3, and 4-7 (every solve rewrites 4-6)
         if (e != hipSuccess) return (int)e;
     }
@@ -134,7 +148,7 @@ extern "C" int lrs_svt_gram_f32(const float *X, const float *L2, float c2, int64
     hipLaunchKernelGGL(k_gram_reduce16, dim3((unsigned)((Bp * Bp + 255) / 256)), dim3(256), 0, st, w.partial, nslab,
                        sh.gram_nt, (int)B, Bp, w.G);
     LRS_CHECK_LAUNCH();
-    if ((warm & LRS_SVT_WARM) && ((warm & LRS_SVT_JACOBI) || sh.wide) && !wide_tri) {
+    if (plan.warm_products) {
         // A0 = V^T (G V) with the current V (unused when V is not valid yet: Jacobi starts from G)
         const dim3 g16((Bp + 15) / 16, (Bp + 15) / 16);
         hipLaunchKernelGGL(k_gemm_f64_state, g16, dim3(256), 0, st, w, 0);
@@ -156,117 +170,128 @@ static int svt_apply(const float *X, const float *L2, float c2, int64_t P, int64
     return LRS_OK;
 }
 
-// Stage 2: one-workgroup eigensolver (runs beside the sparse-coding kernel), E, U.
+// Stage 2's launchers, one per chain.  What they share: the workspace, this band count's forms, and the LDS of
+// the Jacobi solve (smem) and the V replay (vsmem), of the tridiagonal stage (tsmem: the packed triangle unless
+// ga, + p vector) and the most a phase of the narrow tridiagonal chains needs (lds: the products' staging too).
+struct SvtSolve {
+    SvtWs w;
+    int B, Bp;
+    double tau;
+    SvtShape sh;
+    SvtKernels k;
+    size_t smem, vsmem, tsmem, lds;
+    hipStream_t st;
+};
+// one launch on the call's stream, the workspace first among the kernel's arguments, and its check
+#define SVT_LAUNCH(c, kernel, grid, block, lds, ...)                                \
+    do {                                                                            \
+        hipLaunchKernelGGL(kernel, grid, block, lds, (c).st, (c).w, ##__VA_ARGS__); \
+        LRS_CHECK_LAUNCH();                                                         \
+    } while (0)
+
+// dynamic LDS above 64 KiB must be opted into; request exactly what this shape needs
+static const auto opt_in = [](const void *kernel, size_t bytes) {
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+};
+
+// eigenvalues, inverse iteration and back-transformation of a tridiagonal chain over many workgroups
+static int svt_vals_vecs_back(const SvtSolve &c, TriKernel vals, TriKernel vecs, TriKernel back) {
+    SVT_LAUNCH(c, vals, dim3((unsigned)((4 * c.Bp + kEigMwThreads - 1) / kEigMwThreads)), dim3(kEigMwThreads), 0);
+    SVT_LAUNCH(c, vecs, dim3((unsigned)((c.Bp + kEigMwThreads - 1) / kEigMwThreads)), dim3(kEigMwThreads), 0);
+    SVT_LAUNCH(c, back, dim3((unsigned)((c.Bp + 15) / 16)), dim3(256), 0);
+    return LRS_OK;
+}
+
+// E, and F = I - E in w.Fp, after a chain that does not write them itself
+static int svt_build_E(const SvtSolve &c) {
+    SVT_LAUNCH(c, k_build_E, dim3((unsigned)((c.B + 15) / 16), (unsigned)((c.B + 15) / 16)), dim3(256), 0, c.B, c.tau);
+    return LRS_OK;
+}
+
+static int svt_run_tri(const SvtSolve &c) {
+    const hipError_t ea = opt_in((const void *)c.k.eig, c.lds);
+    if (ea != hipSuccess) return (int)ea;
+    SVT_LAUNCH(c, c.k.eig, dim3(1), dim3(kEigThreads), c.lds, c.B, c.tau);
+    return LRS_OK;
+}
+
+// the phases of k_svt_eig as five kernels, three of them over many workgroups
+static int svt_run_tri_mw(const SvtSolve &c) {
+    hipError_t ea = opt_in((const void *)c.k.tri, c.tsmem);
+    if (ea == hipSuccess) ea = opt_in((const void *)c.k.cert, c.lds);
+    if (ea != hipSuccess) return (int)ea;
+    SVT_LAUNCH(c, c.k.tri, dim3(1), dim3(kEigThreads), c.tsmem);
+    const int rc = svt_vals_vecs_back(c, k_svt_eig_vals, k_svt_eig_vecs, k_svt_eig_back);
+    if (rc != LRS_OK) return rc;
+    SVT_LAUNCH(c, c.k.cert, dim3(1), dim3(kEigThreads), c.lds, c.B, c.tau);
+    return LRS_OK;
+}
+
+// narrow and wide alike: the shape class picks k_jacobi_lds<ga> and the replay's rows
+static int svt_run_jacobi(const SvtSolve &c, int jwarm) {
+    hipError_t ea = opt_in((const void *)c.k.jacobi, c.smem);
+    if (ea == hipSuccess) ea = opt_in((const void *)k_jacobi_vrebuild, c.vsmem);
+    if (ea != hipSuccess) return (int)ea;
+    SVT_LAUNCH(c, c.k.jacobi, dim3(1), dim3(kJacobiThreads), c.smem, jwarm);
+    const dim3 vgrid((unsigned)((c.Bp + c.sh.vrows - 1) / c.sh.vrows));
+    SVT_LAUNCH(c, k_jacobi_vrebuild, vgrid, dim3(1024), c.vsmem, jwarm);
+    SVT_LAUNCH(c, k_svt_finish_state, dim3(1), dim3(1), 0);
+    return svt_build_E(c);
+}
+
+// tridiagonalisation, eigenvalues, inverse iteration, back-transformation; S = V^T V and its
+// certificate, kWtMaxNs gated Newton-Schulz steps, the gated Jacobi fallback; then E
+static int svt_run_wide_tri(const SvtSolve &c, bool mw_reduction) {
+    const int Bp = c.Bp;
+    const hipError_t ea = opt_in((const void *)k_svt_eig_wide_fb_vrebuild, c.vsmem);
+    if (ea != hipSuccess) return (int)ea;
+    if (mw_reduction) {
+        // the reduction over many workgroups: launch k forms reflector k + 1 and applies reflector k
+        for (int kc = -1; kc <= Bp - 2; ++kc)
+            SVT_LAUNCH(c, k_svt_eig_wide_mw, dim3((unsigned)mw_nwg(Bp, kc)), dim3(kMwThreads), 0, kc);
+    } else {
+        SVT_LAUNCH(c, k_svt_eig_wide_tri, dim3(1), dim3(kEigThreads), sizeof(double) * Bp);
+    }
+    const int rc = svt_vals_vecs_back(c, k_svt_eig_wide_vals, k_svt_eig_wide_vecs, k_svt_eig_wide_back);
+    if (rc != LRS_OK) return rc;
+    const dim3 g64((unsigned)((Bp + 63) / 64), (unsigned)((Bp + 63) / 64));
+    for (int step = 0; step <= kWtMaxNs; ++step) {
+        if (step > 0) SVT_LAUNCH(c, k_svt_eig_wide_gemm<true>, g64, dim3(256), 0, step);
+        SVT_LAUNCH(c, k_svt_eig_wide_gemm<false>, g64, dim3(256), 0, step);
+        SVT_LAUNCH(c, k_svt_eig_wide_cert, dim3(1), dim3(kEigThreads), 0, step);
+    }
+    SVT_LAUNCH(c, k_svt_eig_wide_fb_jacobi, dim3(1), dim3(kJacobiThreads), c.smem);
+    const dim3 vgrid((unsigned)((Bp + c.sh.vrows - 1) / c.sh.vrows));
+    SVT_LAUNCH(c, k_svt_eig_wide_fb_vrebuild, vgrid, dim3(1024), c.vsmem);
+    SVT_LAUNCH(c, k_svt_eig_wide_fb_state, dim3(1), dim3(1), 0);
+    return svt_build_E(c);
+}
+
+// Stage 2: the plan's eigen chain (runs beside the sparse-coding kernel), E, U.
 extern "C" int lrs_svt_finish_f32(const float *X, const float *L2, float c2, int64_t P, int64_t B, double tau,
                                   float *U, double *s_out, int warm, void *ws, size_t ws_bytes, void *stream) {
     if (!X || !U || !ws || P <= 0 || B <= 0 || tau < 0.0) return LRS_E_INVALID;
-    if (svt_shape_check(B, warm) != LRS_OK) return LRS_E_UNSUPPORTED;
+    const SvtPlan plan = svt_plan(B, warm);
+    if (plan.rc != LRS_OK) return plan.rc;
     if (ws_bytes < svt_ws_offsets(B).total) return LRS_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    SvtWs w = svt_ws_layout(ws, B);
-    const int Bp = (int)w.Bp;
     const SvtShape sh = svt_shape(B);
-    const SvtKernels k = svt_kernels(sh);
-    // dynamic LDS above 64 KiB must be opted into; request exactly what this shape needs
-    auto opt_in = [](const void *kernel, size_t bytes) {
-        return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    };
-    const size_t smem = jacobi_lds(Bp, sh.ga);
-    const size_t vsmem = vrebuild_lds(Bp);
-    const bool wide_tri = svt_wide_tri(B, warm);
-    warm = svt_flags(B, warm);
-    if (wide_tri) {
-        // tridiagonalisation, eigenvalues, inverse iteration, back-transformation; S = V^T V and its
-        // certificate, kWtMaxNs gated Newton-Schulz steps, the gated Jacobi fallback; then E as below
-        hipError_t ea = opt_in((const void *)k_svt_eig_wide_fb_vrebuild, vsmem);
-        if (ea != hipSuccess) return (int)ea;
-        const dim3 g64((unsigned)((Bp + 63) / 64), (unsigned)((Bp + 63) / 64));
-        if (warm & LRS_SVT_WIDE_MW) {
-            // the reduction over many workgroups: launch k forms reflector k + 1 and applies reflector k
-            for (int kc = -1; kc <= Bp - 2; ++kc) {
-                hipLaunchKernelGGL(k_svt_eig_wide_mw, dim3((unsigned)mw_nwg(Bp, kc)), dim3(kMwThreads), 0, st, w, kc);
-                LRS_CHECK_LAUNCH();
-            }
-        } else {
-            hipLaunchKernelGGL(k_svt_eig_wide_tri, dim3(1), dim3(kEigThreads), sizeof(double) * Bp, st, w);
-            LRS_CHECK_LAUNCH();
-        }
-        hipLaunchKernelGGL(k_svt_eig_wide_vals, dim3((unsigned)((4 * Bp + kEigMwThreads - 1) / kEigMwThreads)),
-                           dim3(kEigMwThreads), 0, st, w);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_svt_eig_wide_vecs, dim3((unsigned)((Bp + kEigMwThreads - 1) / kEigMwThreads)),
-                           dim3(kEigMwThreads), 0, st, w);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_svt_eig_wide_back, dim3((unsigned)((Bp + 15) / 16)), dim3(256), 0, st, w);
-        LRS_CHECK_LAUNCH();
-        for (int step = 0; step <= kWtMaxNs; ++step) {
-            if (step > 0) {
-                hipLaunchKernelGGL(k_svt_eig_wide_gemm<true>, g64, dim3(256), 0, st, w, step);
-                LRS_CHECK_LAUNCH();
-            }
-            hipLaunchKernelGGL(k_svt_eig_wide_gemm<false>, g64, dim3(256), 0, st, w, step);
-            LRS_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_svt_eig_wide_cert, dim3(1), dim3(kEigThreads), 0, st, w, step);
-            LRS_CHECK_LAUNCH();
-        }
-        hipLaunchKernelGGL(k_svt_eig_wide_fb_jacobi, dim3(1), dim3(kJacobiThreads), smem, st, w);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_svt_eig_wide_fb_vrebuild, dim3((unsigned)((Bp + sh.vrows - 1) / sh.vrows)), dim3(1024),
-                           vsmem, st, w);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_svt_eig_wide_fb_state, dim3(1), dim3(1), 0, st, w);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_build_E, dim3((unsigned)((B + 15) / 16), (unsigned)((B + 15) / 16)), dim3(256), 0, st,
-                           w, (int)B, tau);
-        LRS_CHECK_LAUNCH();
-    } else if (sh.wide || (warm & LRS_SVT_JACOBI)) {   // wide: the Jacobi chain unless LRS_SVT_WIDE_TRI asks
-        const int jwarm = warm & LRS_SVT_WARM;
-        hipError_t ea = opt_in((const void *)k.jacobi, smem);
-        if (ea == hipSuccess) ea = opt_in((const void *)k_jacobi_vrebuild, vsmem);
-        if (ea != hipSuccess) return (int)ea;
-        hipLaunchKernelGGL(k.jacobi, dim3(1), dim3(kJacobiThreads), smem, st, w, jwarm);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_jacobi_vrebuild, dim3((unsigned)((Bp + sh.vrows - 1) / sh.vrows)), dim3(1024), vsmem, st,
-                           w, jwarm);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_svt_finish_state, dim3(1), dim3(1), 0, st, w);
-        LRS_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_build_E, dim3((unsigned)((B + 15) / 16), (unsigned)((B + 15) / 16)), dim3(256), 0, st,
-                           w, (int)B, tau);
-        LRS_CHECK_LAUNCH();
-    } else {
-        // the tridiagonal stage's packed triangle (unless ga) + p vector; the products' staging; the fallback
-        const size_t tsmem = sizeof(double) * ((sh.ga ? 0 : (size_t)Bp * (Bp + 1) / 2) + Bp);
-        const size_t esmem = sizeof(double) * 2 * kEKc * eld(sh.nb);
-        const size_t lds = std::max(std::max(tsmem, esmem), std::max(smem, vsmem));
-        if (warm & LRS_SVT_MULTI_WG) {
-            hipError_t ea = opt_in((const void *)k.tri, tsmem);
-            if (ea == hipSuccess) ea = opt_in((const void *)k.cert, lds);
-            if (ea != hipSuccess) return (int)ea;
-            hipLaunchKernelGGL(k.tri, dim3(1), dim3(kEigThreads), tsmem, st, w);
-            LRS_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_svt_eig_vals, dim3((unsigned)((4 * Bp + kEigMwThreads - 1) / kEigMwThreads)),
-                               dim3(kEigMwThreads), 0, st, w);
-            LRS_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_svt_eig_vecs, dim3((unsigned)((Bp + kEigMwThreads - 1) / kEigMwThreads)),
-                               dim3(kEigMwThreads), 0, st, w);
-            LRS_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_svt_eig_back, dim3((unsigned)((Bp + 15) / 16)), dim3(256), 0, st, w);
-            LRS_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k.cert, dim3(1), dim3(kEigThreads), lds, st, w, (int)B, tau);
-            LRS_CHECK_LAUNCH();
-        } else {
-            const hipError_t ea = opt_in((const void *)k.eig, lds);
-            if (ea != hipSuccess) return (int)ea;
-            hipLaunchKernelGGL(k.eig, dim3(1), dim3(kEigThreads), lds, st, w, (int)B, tau);
-            LRS_CHECK_LAUNCH();
-        }
+    const int Bp = (int)(B + (B & 1));
+    const size_t smem = jacobi_lds(Bp, sh.ga), vsmem = vrebuild_lds(Bp);
+    const size_t tsmem = sizeof(double) * ((sh.ga ? 0 : (size_t)Bp * (Bp + 1) / 2) + Bp);
+    const size_t lds = std::max(std::max(tsmem, sizeof(double) * 2 * kEKc * eld(sh.nb)), std::max(smem, vsmem));
+    const SvtSolve c{svt_ws_layout(ws, B), (int)B, Bp, tau, sh, svt_kernels(sh), smem, vsmem, tsmem, lds,
+                     (hipStream_t)stream};
+    int rc = LRS_OK;
+    switch (plan.chain) {
+    case kSvtTri: rc = svt_run_tri(c); break;
+    case kSvtTriMw: rc = svt_run_tri_mw(c); break;
+    case kSvtJacobi:
+    case kSvtWideJacobi: rc = svt_run_jacobi(c, plan.warm); break;
+    case kSvtWideTri: rc = svt_run_wide_tri(c, plan.mw_reduction); break;
     }
-    if (s_out) {
-        hipLaunchKernelGGL(k_sorted_singular_values, dim3(1), dim3(256), 0, st, w, (int)B, s_out);
-        LRS_CHECK_LAUNCH();
-    }
-    return svt_apply(X, L2, c2, P, B, w, U, st);
+    if (rc != LRS_OK) return rc;
+    if (s_out) SVT_LAUNCH(c, k_sorted_singular_values, dim3(1), dim3(256), 0, c.B, s_out);
+    return svt_apply(X, L2, c2, P, B, c.w, U, c.st);
 }
 
 extern "C" int lrs_svt_f32(const float *X, const float *L2, float c2, int64_t P, int64_t B, double tau, float *U,
@@ -283,9 +308,19 @@ extern "C" int lrs_svt_f32(const float *X, const float *L2, float c2, int64_t P,
 // 1 when LRS_SVT_WIDE_MW's reduction produced that chain's triangle; words 8-31 are spare.
 extern "C" int lrs_diag_svt_state(void *ws, int64_t P, int64_t B, int *out32) {
     if (!ws || !out32 || P <= 0 || B <= 0) return LRS_E_INVALID;
-    if (svt_shape_check(B, 0) != LRS_OK) return LRS_E_UNSUPPORTED;
+    if (svt_plan(B, 0).rc != LRS_OK) return LRS_E_UNSUPPORTED;
     SvtWs w = svt_ws_layout(ws, B);
     return (int)hipMemcpy(out32, w.state, 32 * sizeof(int), hipMemcpyDeviceToHost);
+}
+
+// Diagnostics (host only, no device touched): the plan of (B, flags) as chain (SvtChain), warm,
+// mw_reduction, reset_state, warm_products; words 5-7 are spare.  Returns the plan's return code.
+extern "C" int lrs_diag_svt_plan(int64_t B, int flags, int *out8) {
+    if (B <= 0 || !out8) return LRS_E_INVALID;
+    const SvtPlan p = svt_plan(B, flags);
+    const int words[8] = {p.chain, p.warm, p.mw_reduction, p.reset_state, p.warm_products, 0, 0, 0};
+    std::copy(words, words + 8, out8);
+    return p.rc;
 }
 
 // Diagnostics: the SVT apply alone (F = I - E from the last solve in ws): the kernel
@@ -293,6 +328,6 @@ extern "C" int lrs_diag_svt_state(void *ws, int64_t P, int64_t B, int *out32) {
 extern "C" int lrs_diag_svt_apply(const float *X, const float *L2, float c2, int64_t P, int64_t B, void *ws, float *U,
                                   void *stream) {
     if (!X || !U || !ws || P <= 0 || B <= 0) return LRS_E_INVALID;
-    if (svt_shape_check(B, 0) != LRS_OK) return LRS_E_UNSUPPORTED;
+    if (svt_plan(B, 0).rc != LRS_OK) return LRS_E_UNSUPPORTED;
     return svt_apply(X, L2, c2, P, B, svt_ws_layout(ws, B), U, (hipStream_t)stream);
 }

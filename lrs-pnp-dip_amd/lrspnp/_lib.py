@@ -74,6 +74,8 @@ _FRAME = ("lrs_masked_mse_framed_f32", "lrs_unfolded_to_frame_f32", "lrs_frame_t
           "lrs_dipnet_set_frame", "lrs_dipnet_get_frame")
 # ... and the TV term of the DIP output and the TV prox on the cube
 _TV = ("lrs_sstv_f32", "lrs_tvprox_workspace", "lrs_tvprox_f32")
+# ... and the host-only diagnostic of the SVT calls' resolved chain
+_SVT_PLAN = ("lrs_diag_svt_plan",)
 
 
 def build(force: bool = False) -> str:
@@ -126,6 +128,7 @@ def _declare(L):
         "lrs_svt_finish_f32": (i32, [vp, vp, f32, i64, i64, f64, vp, vp, i32, vp, sz, vp]),
         "lrs_svt_gram_offset": (i32, [i64, i64, vp, vp]),
         "lrs_diag_svt_state": (i32, [vp, i64, i64, vp]),
+        "lrs_diag_svt_plan": (i32, [i64, i32, i32p]),
         "lrs_diag_svt_apply": (i32, [vp, vp, f32, i64, i64, vp, vp, vp]),
         "lrs_tvprox_workspace": (sz, [i64, i64, i64]),
         "lrs_tvprox_f32": (i32, [vp, vp, f32, i64, i64, i64, f32, f32, f32, f64, i32, i32, vp, vp, vp, sz, vp]),
@@ -191,7 +194,7 @@ def _declare(L):
         "lrs_stream_wait": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
-        if name in _PER_BAND_MASK + _FRAME + _TV and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
+        if name in _PER_BAND_MASK + _FRAME + _TV + _SVT_PLAN and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
             continue   # an A/B build from before these: its other paths still time against this one
         fn = getattr(L, name)
         fn.restype = res

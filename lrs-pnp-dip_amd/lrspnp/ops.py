@@ -15,7 +15,7 @@ from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLA
                    SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, TVPROX_WARM, LrsError, check, device_lib, ista_accel, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "tvprox_workspace", "tvprox", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "svt_plan", "tvprox_workspace", "tvprox", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -335,6 +335,19 @@ def _svt_flags(warm, method, multi_wg=False, wide_tri=False, wide_mw=False):
         raise LrsError(f"unknown SVT eigensolver {method!r} (tri | jacobi)")
     return ((SVT_WARM if warm else 0) | (SVT_JACOBI if method == "jacobi" else 0) | (SVT_MULTI_WG if multi_wg else 0)
             | (SVT_WIDE_TRI if wide_tri else 0) | (SVT_WIDE_MW if wide_mw else 0))
+
+
+SVT_CHAINS = ("tri", "tri-multi-wg", "jacobi", "wide-jacobi", "wide-tri")
+
+
+def svt_plan(B: int, warm=False, method="tri", multi_wg=False, wide_tri=False, wide_mw=False) -> dict:
+    """What the SVT calls do with B bands and these keywords of svt() (lrs_diag_svt_plan; host-only): the
+    eigen chain (one of SVT_CHAINS), whether it warm-starts, whether the wide tridiagonal chain's reduction
+    runs over many workgroups, and whether svt_gram() zeroes the state words / forms the warm-start products."""
+    out = (ctypes.c_int32 * 8)()
+    check(lib().lrs_diag_svt_plan(int(B), _svt_flags(warm, method, multi_wg, wide_tri, wide_mw), out), "lrs_diag_svt_plan")
+    return dict(chain=SVT_CHAINS[out[0]], warm=bool(out[1]), mw_reduction=bool(out[2]), reset_state=bool(out[3]),
+                warm_products=bool(out[4]))
 
 
 def svt(X, L2, c2: float, tau: float, ws, U=None, s_out=None, warm=False, stream=None, method="tri",

@@ -137,12 +137,21 @@ _ALPHA = {"spec2": ops.ALPHA_SPEC2, "fro4": ops.ALPHA_FRO4, "soft": ops.ALPHA_SO
 _PROX = {"spec2": ops.PROX_NLM, "fro4": ops.PROX_NLM, "soft": ops.PROX_SOFT, "matlab": ops.PROX_NLM_MATLAB}
 # LrsPnPConfig.svt_wide_solver -> (wide_tri, wide_mw) of the SVT calls
 _SVT_WIDE_SOLVER = {"jacobi": (False, False), "tri": (True, False), "tri-mw": (True, True)}
+# LrsPnPConfig's mode strings and their values: LrsPnP.__init__ checks every one before any device work
+_MODES = {"variant": tuple(_PROX), "lowrank": ("svt", "dip", "tv"), "svt_method": ("tri", "jacobi"),
+          "svt_multi_wg": ("auto", "on", "off"), "svt_wide_solver": tuple(_SVT_WIDE_SOLVER),
+          "ista_patterns": ("auto", "on", "off"), "ista_dip_order": ("beside", "before"),
+          "ista_accel": ("off", "fista")}
+
+
+def _check_mode(name, value):
+    if value not in _MODES[name]:
+        raise LrsError(f"unknown {name} {value!r} ({' | '.join(_MODES[name])})")
 
 
 def svt_wide_solver_flags(name):
     """(wide_tri, wide_mw) for a value of LrsPnPConfig.svt_wide_solver (host-only)."""
-    if name not in _SVT_WIDE_SOLVER:
-        raise LrsError(f"unknown svt_wide_solver {name!r} ({' | '.join(_SVT_WIDE_SOLVER)})")
+    _check_mode("svt_wide_solver", name)
     return _SVT_WIDE_SOLVER[name]
 
 
@@ -159,6 +168,13 @@ class LrsPnP:
         no network engine -- a task-parallel worker rank that never trains the DIP
         (lrspnp.dist.DipTaskSplit)."""
         self.cfg = cfg = cfg or LrsPnPConfig()
+        for name in _MODES:   # every mode string, before anything is copied or enqueued
+            _check_mode(name, getattr(cfg, name))
+        if cfg.ista_accel != "off" and int(cfg.ista_slices_dip) > 1:
+            raise LrsError("ista_accel='fista' with ista_slices_dip > 1: every accelerated call restarts its "
+                           "momentum, so the slices would not be one call")
+        if comm is not None and (cfg.lowrank != "svt" or cfg.svt_method != "tri"):
+            raise LrsError("a row-slab shard needs lowrank='svt' with svt_method='tri'")
         # comm: None (whole cube here) or a row-slab communicator (lrspnp.dist.SlabComm): Y, M are
         # then this rank's pixel-row slab and the SVT Gram / convergence sums are all-reduced
         self.comm = comm
@@ -177,11 +193,8 @@ class LrsPnP:
             D, self.dict_history = learn_dictionary(self.Y, self.M, dcfg, device=dev)
         self.D = f(D)
         self.P, self.B = self.Y.shape
-        # above 256 bands the SVT's eigen stage is the warm-started Jacobi chain, whose warm-start
-        # products read the Gram inside svt_gram(): no all-reduce in between, and the sparse coding
-        # waits for the Gram as it does for svt_method='jacobi'
-        self.svt_wide = cfg.lowrank == "svt" and self.B > 256
-        if self.svt_wide:
+        wide = cfg.lowrank == "svt" and self.B > 256
+        if wide:
             if self.B > ops.svt_max_bands():
                 raise LrsError(f"lowrank='svt' takes at most {ops.svt_max_bands()} bands, got {self.B}")
             if comm is not None:
@@ -189,6 +202,21 @@ class LrsPnP:
                                "of sharded SVT (lrs_svt_gram_offset)")
             if cfg.svt_multi_wg == "on":
                 raise LrsError(f"svt_multi_wg='on' needs at most 256 bands, got {self.B}")
+        # The SVT's solver, resolved once: the keywords of ops.svt_gram; those of ops.svt / ops.svt_finish, which add
+        # the many-workgroup tridiagonal chain ("auto": on a row-slab shard); whether the sparse coding waits for
+        # the Gram (above 256 bands as for svt_method='jacobi': the default eigen stage there is the warm-started
+        # Jacobi chain, whose warm-start products read the Gram inside svt_gram(), so no all-reduce in between)
+        wide_tri, wide_mw = svt_wide_solver_flags(cfg.svt_wide_solver)
+        self._svt_gram_kw = dict(method=cfg.svt_method, wide_tri=wide and wide_tri, wide_mw=wide and wide_mw)
+        self._svt_kw = dict(self._svt_gram_kw, multi_wg=cfg.svt_multi_wg == "on" or (
+            cfg.svt_multi_wg == "auto" and comm is not None))
+        self._gram_gates = cfg.svt_gram_first or cfg.svt_method == "jacobi" or wide
+        if cfg.lowrank != "svt":
+            if image_shape is None:
+                raise LrsError(f"lowrank={cfg.lowrank!r} needs image_shape=(H, W) with H*W = P")
+            self.H, self.W = (int(v) for v in image_shape)
+            if self.H * self.W != self.P:
+                raise LrsError(f"image_shape {self.H}x{self.W} does not match P = {self.P}")
         n, self.K = self.D.shape
         if n != cfg.bb * cfg.bb:
             raise LrsError(f"dictionary has {n} rows, expected bb*bb = {cfg.bb * cfg.bb}")
@@ -198,8 +226,6 @@ class LrsPnP:
         self.gamma32, self.mu1_32, self.mu2_32 = f32(cfg.gamma), f32(cfg.mu1), f32(cfg.mu2)
         self.c2 = f32(1 / cfg.mu2)                        # (1/mu_2)*lambda_2   main_LRS_PnP.py:315
         self.tau = float(f32(1 / cfg.mu2))                # SVT threshold (float32 in numpy)
-        if cfg.variant not in _PROX:
-            raise LrsError(f"unknown ISTA variant {cfg.variant!r} (spec2 | fro4 | soft | matlab)")
         self.prox = _PROX[cfg.variant]
 
         # ---- block grid (host bookkeeping) -------------------------------------------------
@@ -230,20 +256,6 @@ class LrsPnP:
         self.thr = thr_pat.index_select(0, inv_d).contiguous()
         self.alpha_pat, self.thr_pat, self.obs_pat = alpha_pat, thr_pat, obs_pat
         self.pat_plan = None
-        if cfg.ista_patterns not in ("auto", "on", "off"):
-            raise LrsError(f"unknown ista_patterns {cfg.ista_patterns!r} (auto | on | off)")
-        # every mode string is checked here, before anything is enqueued (not halfway through step())
-        if cfg.ista_dip_order not in ("beside", "before"):
-            raise LrsError(f"unknown ista_dip_order {cfg.ista_dip_order!r} (beside | before)")
-        if cfg.svt_multi_wg not in ("auto", "on", "off"):
-            raise LrsError(f"unknown svt_multi_wg {cfg.svt_multi_wg!r} (auto | on | off)")
-        if cfg.ista_accel not in ("off", "fista"):
-            raise LrsError(f"unknown ista_accel {cfg.ista_accel!r} (off | fista)")
-        if cfg.ista_accel != "off" and int(cfg.ista_slices_dip) > 1:
-            raise LrsError("ista_accel='fista' with ista_slices_dip > 1: every accelerated call restarts its "
-                           "momentum, so the slices would not be one call")
-        wide_tri, wide_mw = svt_wide_solver_flags(cfg.svt_wide_solver)
-        self.svt_wide_tri, self.svt_wide_mw = self.svt_wide and wide_tri, self.svt_wide and wide_mw
         if self.K <= 512 and (cfg.ista_patterns == "on" or (
                 cfg.ista_patterns == "auto" and ops.ista_pat_preferred(n, self.K, self.nb, self.npat, cfg.Nit))):
             plan, self.pat_ntiles = ops.ista_pat_plan(inv.reshape(-1), self.npat)
@@ -264,35 +276,25 @@ class LrsPnP:
         self.lowrank_stream = torch.cuda.Stream(device=dev, priority=int(cfg.lowrank_priority))
         self.iteration = 0
         self.dip = None
-        if comm is not None and (cfg.lowrank != "svt" or cfg.svt_method != "tri"):
-            raise LrsError("a row-slab shard needs lowrank='svt' with svt_method='tri'")
+        self._rs_ws = self._coefs = None   # made by the first call that needs one (sparse_coding_range; sliced step)
+        # beside the DIP training the sparse coding may be narrowed, or (row-split kernel: warm start) sliced
+        dip, rs = cfg.lowrank == "dip", self.n_pad > 64 and self.K <= 512
+        self._max_wg = cfg.ista_max_wg_dip if dip else 0
+        self._slices = max(1, min(int(cfg.ista_slices_dip), cfg.Nit)) if dip and rs else 1
         if cfg.lowrank == "svt":
             self.svt_ws = ops.svt_workspace(self.P, self.B, dev)
             self.gram = ops.svt_gram_view(self.svt_ws, self.P, self.B) if comm is not None else None
-        elif cfg.lowrank == "dip":
-            self._init_dip(image_shape, dev, engine=dip_engine)
-        elif cfg.lowrank == "tv":
-            if image_shape is None:
-                raise LrsError("lowrank='tv' needs image_shape=(H, W) with H*W = P")
-            H, W = (int(v) for v in image_shape)
-            if H * W != self.P:
-                raise LrsError(f"image_shape {H}x{W} does not match P = {self.P}")
-            self.H, self.W = H, W
-            self.tv = cfg.tv or TvProxConfig()
-            self.tv_ws = ops.tvprox_workspace(H, W, self.B, dev)
+        elif dip:
+            self._init_dip(dev, engine=dip_engine)
         else:
-            raise LrsError(f"unknown lowrank prox {cfg.lowrank!r} (svt | dip | tv)")
+            self.tv = cfg.tv or TvProxConfig()
+            self.tv_ws = ops.tvprox_workspace(self.H, self.W, self.B, dev)
 
-    def _init_dip(self, image_shape, dev, engine=True):
+    def _init_dip(self, dev, engine=True):
         """DIP target = the observed cube as an image, mask_bkg = the pixel mask
         (…1-LiP.py:275-301); the network is re-initialised every outer iteration (:214)."""
         from .dip import DipConfig, LipschitzDip, dip_nodes, frame_for
-        if image_shape is None:
-            raise LrsError("lowrank='dip' needs image_shape=(H, W) with H*W = P")
-        H, W = (int(v) for v in image_shape)
-        if H * W != self.P:
-            raise LrsError(f"image_shape {H}x{W} does not match P = {self.P}")
-        self.H, self.W = H, W
+        H, W = self.H, self.W
         dcfg = self.cfg.dip or DipConfig()
         self.dip = LipschitzDip(self.B, H, W, dcfg, device=dev,
                                  stream_priority=self.cfg.lowrank_priority) if engine else None
@@ -328,9 +330,12 @@ class LrsPnP:
     # -----------------------------------------------------------------------------------------
     def sparse_coding(self, stream=None, want_coefs=False):
         """Yb = blocks of X + L1/mu1; Phi = D * ISTA-PnP(Yb) for every block."""
-        ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
-                   stream=stream)
+        self._im2col(stream)
         return self._ista(self.cfg.Nit, stream, want_coefs=want_coefs)
+
+    def _im2col(self, stream, blocks=slice(None)):
+        ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d[blocks], self.cols_d[blocks], self.n_pad,
+                   Yb=self.Yb[blocks], stream=stream)
 
     def _ista(self, Nit, stream, want_coefs=False, coefs=None, warm_start=False, max_workgroups=0):
         """All blocks' ISTA into self.phi: the per-pattern Gram path when planned, else lrs_ista_f32."""
@@ -347,11 +352,10 @@ class LrsPnP:
         """Phi rows [b0, b1) only (the blocks of one task-parallel worker, lrspnp.dist.DipTaskSplit)."""
         if b1 <= b0:
             return
-        ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d[b0:b1], self.cols_d[b0:b1], self.n_pad,
-                   Yb=self.Yb[b0:b1], stream=stream)
+        self._im2col(stream, slice(b0, b1))
         ws = self.ista_ws
         if self.pat_plan is not None:   # a block range runs the row-split kernel, on a workspace of its own
-            if getattr(self, "_rs_ws", None) is None:
+            if self._rs_ws is None:
                 self._rs_ws = ops.ista_workspace(self.n, self.K, self.prox, self.Yb.device, accel=self.cfg.ista_accel)
             ws = self._rs_ws
         ops.ista(self.Yb[b0:b1], self.obs[b0:b1], self.D, self.n, self.alpha[b0:b1], self.thr[b0:b1], self.cfg.Nit,
@@ -371,11 +375,12 @@ class LrsPnP:
                           w_ss=tv.w_ss, tau=self.tau, n_iter=tv.n_iter, warm=tv.warm and self.iteration > 0,
                           stats=stats, stream=stream)
 
+    def _svt_warm(self):
+        return self.cfg.svt_warm and self.iteration > 0
+
     def low_rank(self, stream=None, s_out=None):
-        warm = self.cfg.svt_warm and self.iteration > 0
-        return ops.svt(self.X, self.L2, self.c2, self.tau, self.svt_ws, U=self.U, s_out=s_out, warm=warm,
-                       stream=stream, method=self.cfg.svt_method, wide_tri=self.svt_wide_tri,
-                       wide_mw=self.svt_wide_mw)
+        return ops.svt(self.X, self.L2, self.c2, self.tau, self.svt_ws, U=self.U, s_out=s_out, warm=self._svt_warm(),
+                       stream=stream, **self._svt_kw)
 
     def low_rank_dip(self, stream):
         """U = DIP(X + L2/mu2) (…1-LiP.py:399-411) on `stream`; the host polls early stopping."""
@@ -396,88 +401,53 @@ class LrsPnP:
                 ops.image_to_unfolded(img, self.H, self.W, self.U, stream=stream)
         self.dip_steps.append((self.dip.last_steps, self.dip.last_stop_epoch))
 
-    def step(self):
-        """One outer ADMM iteration (main_LRS_PnP.py:250-366), stream-ordered.  No host sync in
-        the SVT and TV modes; the DIP mode polls its early-stopping flag on the low-rank stream only."""
-        if self.cfg.lowrank == "dip":
-            if self.dip is None:
-                raise LrsError("this LrsPnP was built without a DIP engine (dip_engine=False)")
-            return self._step_dip()
-        if self.cfg.lowrank == "tv":
-            return self._step_tv()
-        main = torch.cuda.current_stream()
-        lr = self.lowrank_stream
-        warm = self.cfg.svt_warm and self.iteration > 0
-        stream_wait(lr, main)
-        # low-rank prox, first half (whole chip, ~0.2 ms): fp64 Gram (+ Jacobi warm-start products)
-        ops.svt_gram(self.X, self.L2, self.c2, self.svt_ws, warm=warm, stream=lr, method=self.cfg.svt_method,
-                     wide_tri=self.svt_wide_tri, wide_mw=self.svt_wide_mw)
+    # The per-mode parts of step(): early(lr) is enqueued before im2col and may return an event the sparse
+    # coding waits for; late(main, lr) is enqueued after the sparse coding.
+    def _svt_early(self, lr):
+        warm = self._svt_warm()   # first half (whole chip, ~0.2 ms): fp64 Gram (+ Jacobi warm-start products)
+        ops.svt_gram(self.X, self.L2, self.c2, self.svt_ws, warm=warm, stream=lr, **self._svt_gram_kw)
         if self.comm is not None:
             self.comm.allreduce_(self.gram, lr)       # the cube's Gram = sum of the slabs' Grams
         gram_done = lr.record_event()
         # second half: the one-workgroup eigensolver then runs beside the sparse coding
-        mw = self.cfg.svt_multi_wg
-        if mw not in ("auto", "on", "off"):
-            raise LrsError(f"unknown svt_multi_wg {mw!r} (auto | on | off)")
-        ops.svt_finish(self.X, self.L2, self.c2, self.tau, self.svt_ws, self.U, warm=warm, stream=lr,
-                       method=self.cfg.svt_method, multi_wg=mw == "on" or (mw == "auto" and self.comm is not None),
-                       wide_tri=self.svt_wide_tri, wide_mw=self.svt_wide_mw)
-        ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
-                   stream=main)
-        if self.cfg.svt_gram_first or self.cfg.svt_method == "jacobi" or self.svt_wide:
-            # the Gram gets the chip before the sparse-coding kernel fills it, so the ~7 ms Jacobi
-            # solve starts at once; the tridiagonal chain fits inside the sparse coding even when
-            # its Gram waits for the first sparse-coding workgroups to retire
-            main.wait_event(gram_done)
-        self._ista(self.cfg.Nit, main)
-        stream_wait(main, lr)
-        ops.admm_update(self.X, self.L1, self.L2, self.Y, self.M, self.U, self.phi, self.cfg.bb, self.grid,
-                        self.gamma32, self.mu1_32, self.mu2_32, norms=self.norms, stream=main)
-        self.iteration += 1
+        ops.svt_finish(self.X, self.L2, self.c2, self.tau, self.svt_ws, self.U, warm=warm, stream=lr, **self._svt_kw)
+        # gated: the Gram gets the chip before the sparse coding fills it, so the ~7 ms Jacobi solve starts at once;
+        # the tridiagonal chain fits inside the sparse coding even when its Gram waits for workgroups to retire
+        return gram_done if self._gram_gates else None
 
-    def _step_tv(self):
-        main = torch.cuda.current_stream()
-        lr = self.lowrank_stream
-        stream_wait(lr, main)
-        # the TV prox's stencil passes run beside im2col and the sparse coding; no host sync
-        self.low_rank_tv(lr)
-        ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
-                   stream=main)
-        self._ista(self.cfg.Nit, main)
-        stream_wait(main, lr)
-        ops.admm_update(self.X, self.L1, self.L2, self.Y, self.M, self.U, self.phi, self.cfg.bb, self.grid,
-                        self.gamma32, self.mu1_32, self.mu2_32, norms=self.norms, stream=main)
-        self.iteration += 1
+    def _tv_early(self, lr):
+        self.low_rank_tv(lr)   # the stencil passes run beside im2col and the sparse coding; no host sync
 
-    def _step_dip(self):
-        main = torch.cuda.current_stream()
-        lr = self.lowrank_stream
-        stream_wait(lr, main)
-        # sparse coding is enqueued first so it runs beside the DIP training
-        ops.im2col(self.X, self.L1, self.mu1_32, self.cfg.bb, self.rows_d, self.cols_d, self.n_pad, Yb=self.Yb,
-                   stream=main)
-        rs = self.n_pad > 64 and self.D.shape[1] <= 512   # the row-split kernel (warm start) serves
-        sl = max(1, min(int(self.cfg.ista_slices_dip), self.cfg.Nit)) if rs else 1
-        if sl == 1:
-            self._ista(self.cfg.Nit, main, max_workgroups=self.cfg.ista_max_wg_dip)
-        else:   # time-sliced: Nit split over `sl` launches continuing from the coefficients
-            if getattr(self, "_coefs", None) is None:
-                self._coefs = torch.empty((self.nb, self.D.shape[1]), dtype=torch.float32, device=self.Yb.device)
-            done = 0
-            for k in range(sl):
-                it = (self.cfg.Nit * (k + 1)) // sl - done
-                self._ista(it, main, coefs=self._coefs, want_coefs=True, warm_start=k > 0,
-                           max_workgroups=self.cfg.ista_max_wg_dip)
-                done += it
+    def _dip_late(self, main, lr):
+        # the sparse coding was enqueued first, so it runs beside the DIP training unless the order says
         if self.cfg.ista_dip_order == "before":
             stream_wait(lr, main)
-        elif self.cfg.ista_dip_order != "beside":
-            raise LrsError(f"unknown ista_dip_order {self.cfg.ista_dip_order!r} (beside | before)")
         self.low_rank_dip(lr)
+
+    _PARTS = {"svt": (_svt_early, None), "tv": (_tv_early, None), "dip": (None, _dip_late)}
+
+    def step(self):
+        """One outer ADMM iteration (main_LRS_PnP.py:250-366), stream-ordered.  No host sync in
+        the SVT and TV modes; the DIP mode polls its early-stopping flag on the low-rank stream only."""
+        if self.cfg.lowrank == "dip" and self.dip is None:
+            raise LrsError("this LrsPnP was built without a DIP engine (dip_engine=False)")
+        early, late = self._PARTS[self.cfg.lowrank]
+        main, lr = torch.cuda.current_stream(), self.lowrank_stream
+        stream_wait(lr, main)
+        gate = early(self, lr) if early else None
+        self._im2col(main)
+        if gate is not None:
+            main.wait_event(gate)
+        Nit, sl = self.cfg.Nit, self._slices
+        if sl > 1 and self._coefs is None:
+            self._coefs = torch.empty((self.nb, self.K), dtype=torch.float32, device=self.Yb.device)
+        for k in range(sl):   # beside the DIP, Nit may be split over launches that continue from the coefficients
+            self._ista(Nit * (k + 1) // sl - Nit * k // sl, main, coefs=self._coefs, want_coefs=sl > 1,
+                       warm_start=k > 0, max_workgroups=self._max_wg)
+        if late:
+            late(self, main, lr)
         stream_wait(main, lr)
-        ops.admm_update(self.X, self.L1, self.L2, self.Y, self.M, self.U, self.phi, self.cfg.bb, self.grid,
-                        self.gamma32, self.mu1_32, self.mu2_32, norms=self.norms, stream=main)
-        self.iteration += 1
+        self.admm(main)
 
     def convergence(self):
         """state_convergence (main_LRS_PnP.py:23-25) of X, lambda_1, lambda_2 for the last step."""
