@@ -331,6 +331,37 @@ int lrs_tvprox_f32(const float *X, const float *L2, float c2, int64_t H, int64_t
                    float w_bd, float w_ss, double tau, int n_iter, int flags, float *U, double *stats, void *ws,
                    size_t ws_bytes, void *stream);
 
+/* ---- Spectral non-local-means prox on the cube: a fourth choice for the low-rank slot --------
+ * An extension (the reference's U update is the SVT or a DIP): the operator of the nlm_prox that
+ * admm_utils.py:95-100 carries beside its tv_prox and never calls, denoise_nl_means(img_HWC,
+ * multichannel=True, sigma, patch_distance=2, h=0.05), as DEFINED here (not bit parity with skimage): one
+ * weight per pixel pair, computed from all bands and applied to every band.
+ * X, L2, U are [P][B] as for the TV prox, P = H W, p = y + H x, the image z[c][y][x];
+ * Z = fl(X + fl(c2 L2)) (L2 nullable: Z = X).  rp = patch_size / 2 with patch_size odd in {1, 3, 5, 7},
+ * rs = patch_distance in 0..5; the host rounds ih2 = (float)(1 / (h h)) and s2 = (float)(2 sigma sigma) once.
+ *   m(e), the index an integer e reads on an axis of length n: 0 when n = 1; else with r = e mod 2 (n - 1)
+ *     (non-negative), r when r < n and 2 (n - 1) - r otherwise: reflection without repeating the edge, continued
+ *     periodically, so defined for every size, those below the pads included
+ *   d(e, e') = sum_c (z[c, m(e)] - z[c, m(e')])^2            over 2-D extended coordinates
+ *   D(p, t)  = sum_{|dy|, |dx| <= rp} d(p + delta, p + delta + t)
+ *   w(p, t)  = exp(-max(D(p, t) / (B (2 rp + 1)^2) - s2, 0) ih2)    so w(p, 0) = 1 exactly
+ *   U[c, p]  = sum_t w(p, t) z[c, p + t] / sum_t w(p, t)
+ * over the offsets t with |ty|, |tx| <= rs whose candidate p + t lies inside the image (the search window is
+ * clipped, not reflected; t = 0 always counts, so the denominator is >= 1).
+ * d is summed in fp32 over the bands in ascending order, D and the weight are formed in fp64 and the weight
+ * is rounded once to fp32, and both sums over t run in fp64 in a fixed order (ty outer, tx inner) without
+ * float atomics: reruns are bit-identical, and so are calls whose bases are aligned differently.
+ * One launch on the caller's stream; the call never allocates and never synchronises, and every refusal is
+ * decided on the host before the launch (the pointers are not read).  ws: lrs_nlmcube_workspace bytes, which
+ * is 0 (the one launch keeps everything in LDS), so ws may be NULL.  U may alias neither X nor L2.
+ * LRS_E_INVALID: X or U NULL, ws NULL while the workspace is > 0, a size <= 0, patch_size even or < 1,
+ * patch_distance < 0, h <= 0, NaN or inf, sigma < 0 or NaN.  LRS_E_UNSUPPORTED: patch_size > 7,
+ * patch_distance > 5, H W B >= 2^31.  LRS_E_WORKSPACE: ws_bytes too small.  An invalid argument wins. */
+size_t lrs_nlmcube_workspace(int64_t H, int64_t W, int64_t B, int patch_size, int patch_distance);
+int lrs_nlmcube_f32(const float *X, const float *L2, float c2, int64_t H, int64_t W, int64_t B,
+                    int patch_size, int patch_distance, double h, double sigma,
+                    float *U, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- col2im + closed-form X update + dual updates ------------------------------------------
  * IMout = sum over covering blocks (block order) of phi, Weight = count, lambda1_sum = repeated
  * sum of lambda_1, then (float32, the reference's operation order)

@@ -5,7 +5,7 @@ liblrspnp_hip.so (csrc/, gfx950).  `LrsPnP` is the batched driver; `compat` re-e
 reference's own function names for drop-in use.
 """
 from ._lib import LrsError, build, lib  # noqa: F401
-from .solver import LrsPnP, LrsPnPConfig, TvProxConfig  # noqa: F401
+from .solver import LrsPnP, LrsPnPConfig, NlmCubeConfig, TvProxConfig  # noqa: F401
 from .dictlearn import DictLearnConfig, learn_dictionary  # noqa: F401
 
 __version__ = "0.2.0"

@@ -74,6 +74,8 @@ _FRAME = ("lrs_masked_mse_framed_f32", "lrs_unfolded_to_frame_f32", "lrs_frame_t
           "lrs_dipnet_set_frame", "lrs_dipnet_get_frame")
 # ... and the TV term of the DIP output and the TV prox on the cube
 _TV = ("lrs_sstv_f32", "lrs_tvprox_workspace", "lrs_tvprox_f32")
+# ... and the non-local-means prox on the cube
+_NLMCUBE = ("lrs_nlmcube_workspace", "lrs_nlmcube_f32")
 # ... and the host-only diagnostic of the SVT calls' resolved chain
 _SVT_PLAN = ("lrs_diag_svt_plan",)
 
@@ -132,6 +134,8 @@ def _declare(L):
         "lrs_diag_svt_apply": (i32, [vp, vp, f32, i64, i64, vp, vp, vp]),
         "lrs_tvprox_workspace": (sz, [i64, i64, i64]),
         "lrs_tvprox_f32": (i32, [vp, vp, f32, i64, i64, i64, f32, f32, f32, f64, i32, i32, vp, vp, vp, sz, vp]),
+        "lrs_nlmcube_workspace": (sz, [i64, i64, i64, i32, i32]),
+        "lrs_nlmcube_f32": (i32, [vp, vp, f32, i64, i64, i64, i32, i32, f64, f64, vp, vp, sz, vp]),
         "lrs_admm_update_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, vp, vp,
                                       vp, vp, f32, f32, f32, vp, vp, vp]),
         # DIP low-rank prox
@@ -194,7 +198,7 @@ def _declare(L):
         "lrs_stream_wait": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
-        if name in _PER_BAND_MASK + _FRAME + _TV + _SVT_PLAN and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
+        if name in _PER_BAND_MASK + _FRAME + _TV + _NLMCUBE + _SVT_PLAN and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
             continue   # an A/B build from before these: its other paths still time against this one
         fn = getattr(L, name)
         fn.restype = res

@@ -15,7 +15,7 @@ from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLA
                    SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, TVPROX_WARM, LrsError, check, device_lib, ista_accel, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "svt_plan", "tvprox_workspace", "tvprox", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "svt_plan", "tvprox_workspace", "tvprox", "nlmcube_workspace", "nlmcube", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -461,6 +461,39 @@ def tvprox(X, L2, c2: float, H: int, W: int, ws, U=None, w_sp: float = 0.0, w_bd
     check(L.lrs_tvprox_f32(_p(X), _p(L2), float(c2), int(H), int(W), B, float(w_sp), float(w_bd), float(w_ss),
                            float(tau), int(n_iter), TVPROX_WARM if warm else 0, _p(U), _p(stats), _p(ws), ws.numel(),
                            _s(stream)), "lrs_tvprox_f32")
+    return U
+
+
+def nlmcube_workspace(H: int, W: int, B: int, patch_size: int, patch_distance: int, device) -> torch.Tensor:
+    """Device workspace of nlmcube() (lrs_nlmcube_workspace).  The one-launch kernel keeps everything in LDS, so
+    the tensor has 0 elements."""
+    n = int(lib().lrs_nlmcube_workspace(int(H), int(W), int(B), int(patch_size), int(patch_distance)))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def nlmcube(X, L2, c2: float, H: int, W: int, ws, U=None, patch_size: int = 7, patch_distance: int = 2, h: float = 0.05,
+            sigma: float = 0.0, stream=None):
+    """U = the spectral non-local means of Z = X + c2*L2 (L2 may be None): one weight per pixel pair from the
+    patch distance over all bands, w = exp(-max(D / (B patch_size^2) - 2 sigma^2, 0) / h^2), applied to every
+    band over the clipped search window |t| <= patch_distance (lrs_nlmcube_f32, include/lrspnp.h, which
+    states the operator).  X (P, B) with P = H*W, p = y + H*x.  patch_size odd, at most 7; patch_distance at
+    most 5.  Returns U."""
+    L = device_lib()
+    _dev(X, torch.float32, "X")
+    if L2 is not None:
+        _dev(L2, torch.float32, "L2")
+    _dev(ws, torch.uint8, "ws")
+    P, B = X.shape
+    if P != H * W:
+        raise LrsError(f"P = {P} != H*W = {H * W}")
+    if U is None:
+        U = torch.empty_like(X)
+    _dev(U, torch.float32, "U")
+    if U.shape != X.shape or (L2 is not None and L2.shape != X.shape):
+        raise LrsError(f"U {tuple(U.shape)} and L2 must have X's shape {tuple(X.shape)}")
+    check(L.lrs_nlmcube_f32(_p(X), _p(L2), float(c2), int(H), int(W), B, int(patch_size), int(patch_distance),
+                            float(h), float(sigma), _p(U), _p(ws) if ws.numel() else None, ws.numel(), _s(stream)),
+          "lrs_nlmcube_f32")
     return U
 
 

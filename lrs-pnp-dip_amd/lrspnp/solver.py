@@ -34,6 +34,29 @@ class TvProxConfig:
 
 
 @dataclass
+class NlmCubeConfig:
+    """lowrank='nlm': the patch size, search radius, filter strength h and noise level sigma of the spectral
+    non-local means U = NLM(X + L2/mu2) (ops.nlmcube).  The defaults are the reference's own call
+    (admm_utils.py:95-100, which it never makes): no quality claim rests on them.  The slot's tau = 1/mu2 is
+    NOT used: sigma is this config's own and is not coupled to mu2."""
+    patch_size: int = 7
+    patch_distance: int = 2
+    h: float = 0.05
+    sigma: float = 0.0
+
+    def check(self):
+        """LrsError for a value lrs_nlmcube_f32 would refuse (host-only)."""
+        if int(self.patch_size) != self.patch_size or self.patch_size not in (1, 3, 5, 7):
+            raise LrsError(f"NlmCubeConfig.patch_size must be 1, 3, 5 or 7, got {self.patch_size!r}")
+        if int(self.patch_distance) != self.patch_distance or not 0 <= self.patch_distance <= 5:
+            raise LrsError(f"NlmCubeConfig.patch_distance must be 0..5, got {self.patch_distance!r}")
+        if not (self.h > 0 and np.isfinite(self.h)):
+            raise LrsError(f"NlmCubeConfig.h must be positive and finite, got {self.h!r}")
+        if not self.sigma >= 0:
+            raise LrsError(f"NlmCubeConfig.sigma must be >= 0, got {self.sigma!r}")
+
+
+@dataclass
 class LrsPnPConfig:
     """The knob table of SURVEY.md §5 (main_LRS_PnP.py:218-238 defaults)."""
     gamma: float = 0.5            # data fidelity                      main_LRS_PnP.py:218
@@ -56,9 +79,11 @@ class LrsPnPConfig:
     # one-workgroup Jacobi chain, 'tri', the tridiagonal chain over many workgroups (LRS_SVT_WIDE_TRI), or
     # 'tri-mw', that chain with its Householder reduction over many workgroups too (+ LRS_SVT_WIDE_MW)
     svt_wide_solver: str = "jacobi"
-    lowrank: str = "svt"          # 'svt' (main_LRS_PnP.py:315), 'dip' (…1-LiP.py:399-411) or 'tv' (TV prox on the cube)
+    # 'svt' (main_LRS_PnP.py:315), 'dip' (…1-LiP.py:399-411), 'tv' (TV prox on the cube) or 'nlm' (spectral NLM on it)
+    lowrank: str = "svt"
     dip: object = None            # lrspnp.dip.DipConfig for lowrank='dip' (None: reference defaults)
     tv: object = None             # TvProxConfig for lowrank='tv' (None: its defaults); the dip fields are ignored there
+    nlm: object = None            # NlmCubeConfig for lowrank='nlm' (None: its defaults)
     dip_seed: int = 0             # DIP init seed of outer iteration t is dip_seed + t
     # Workgroups of the sparse-coding kernel beside the DIP training (lowrank='dip';
     # lrs_ista_opts.max_workgroups, 0 = one per 16-block tile).  Measured at configs[2]
@@ -138,7 +163,7 @@ _PROX = {"spec2": ops.PROX_NLM, "fro4": ops.PROX_NLM, "soft": ops.PROX_SOFT, "ma
 # LrsPnPConfig.svt_wide_solver -> (wide_tri, wide_mw) of the SVT calls
 _SVT_WIDE_SOLVER = {"jacobi": (False, False), "tri": (True, False), "tri-mw": (True, True)}
 # LrsPnPConfig's mode strings and their values: LrsPnP.__init__ checks every one before any device work
-_MODES = {"variant": tuple(_PROX), "lowrank": ("svt", "dip", "tv"), "svt_method": ("tri", "jacobi"),
+_MODES = {"variant": tuple(_PROX), "lowrank": ("svt", "dip", "tv", "nlm"), "svt_method": ("tri", "jacobi"),
           "svt_multi_wg": ("auto", "on", "off"), "svt_wide_solver": tuple(_SVT_WIDE_SOLVER),
           "ista_patterns": ("auto", "on", "off"), "ista_dip_order": ("beside", "before"),
           "ista_accel": ("off", "fista")}
@@ -175,6 +200,8 @@ class LrsPnP:
                            "momentum, so the slices would not be one call")
         if comm is not None and (cfg.lowrank != "svt" or cfg.svt_method != "tri"):
             raise LrsError("a row-slab shard needs lowrank='svt' with svt_method='tri'")
+        if cfg.lowrank == "nlm":
+            (cfg.nlm or NlmCubeConfig()).check()
         # comm: None (whole cube here) or a row-slab communicator (lrspnp.dist.SlabComm): Y, M are
         # then this rank's pixel-row slab and the SVT Gram / convergence sums are all-reduced
         self.comm = comm
@@ -286,9 +313,12 @@ class LrsPnP:
             self.gram = ops.svt_gram_view(self.svt_ws, self.P, self.B) if comm is not None else None
         elif dip:
             self._init_dip(dev, engine=dip_engine)
-        else:
+        elif cfg.lowrank == "tv":
             self.tv = cfg.tv or TvProxConfig()
             self.tv_ws = ops.tvprox_workspace(self.H, self.W, self.B, dev)
+        else:
+            self.nlm = cfg.nlm or NlmCubeConfig()
+            self.nlm_ws = ops.nlmcube_workspace(self.H, self.W, self.B, self.nlm.patch_size, self.nlm.patch_distance, dev)
 
     def _init_dip(self, dev, engine=True):
         """DIP target = the observed cube as an image, mask_bkg = the pixel mask
@@ -375,6 +405,12 @@ class LrsPnP:
                           w_ss=tv.w_ss, tau=self.tau, n_iter=tv.n_iter, warm=tv.warm and self.iteration > 0,
                           stats=stats, stream=stream)
 
+    def low_rank_nlm(self, stream=None):
+        """U = NLM(X + L2/mu2) on `stream` (ops.nlmcube); h and sigma are the config's own, not 1/mu2."""
+        c = self.nlm
+        return ops.nlmcube(self.X, self.L2, self.c2, self.H, self.W, self.nlm_ws, U=self.U, patch_size=c.patch_size,
+                           patch_distance=c.patch_distance, h=c.h, sigma=c.sigma, stream=stream)
+
     def _svt_warm(self):
         return self.cfg.svt_warm and self.iteration > 0
 
@@ -424,7 +460,10 @@ class LrsPnP:
             stream_wait(lr, main)
         self.low_rank_dip(lr)
 
-    _PARTS = {"svt": (_svt_early, None), "tv": (_tv_early, None), "dip": (None, _dip_late)}
+    def _nlm_early(self, lr):
+        self.low_rank_nlm(lr)   # the one launch runs beside im2col and the sparse coding; no host sync
+
+    _PARTS = {"svt": (_svt_early, None), "tv": (_tv_early, None), "nlm": (_nlm_early, None), "dip": (None, _dip_late)}
 
     def step(self):
         """One outer ADMM iteration (main_LRS_PnP.py:250-366), stream-ordered.  No host sync in
