@@ -654,6 +654,40 @@ size_t lrs_psnr_workspace(int64_t P, int64_t B);
 int lrs_psnr_bands_f32(const float *X, const float *C, int64_t P, int64_t B, double *psnr, void *ws,
                        size_t ws_bytes, void *stream);
 
+/* ---- Quality monitor: one pass over X and the clean cube, and a device-side best iterate -------
+ * The scores every reference main prints after an outer iteration (main_LRS_PnP.py:368-391: MPSNR against
+ * the clean image, best_PSNR), with the region restriction and the spectral angle an inpainting run on a
+ * hyperspectral cube is judged by.  X (the solver's X) and C (the clean cube) are [P][B] float32 unfolded;
+ * region is NULL (every entry counts) or u8 [P][B], 1 = counted (1 - M scores the hole alone).  All
+ * arithmetic is fp64 on the float32 inputs.  With r = region[p][b] (1 when NULL):
+ *   n_b = sum_p r,  sse_b = sum_p r (x - c)^2,
+ *   psnr_b = 10 log10(255 / sqrt(sse_b / n_b)), 100 when sse_b / n_b < 1e-10 (as lrs_psnr_bands_f32), NaN when
+ *            n_b = 0;
+ *   q[0] = MPSNR: the mean of psnr_b over the bands with n_b > 0 (NaN when there is none);
+ *   q[1] = SAM in degrees: the mean over the counted pixels of acos(clamp(<x_p, c_p> / (|x_p| |c_p|), -1, 1)),
+ *          the products over all B bands; a pixel counts when region is NULL or any region[p][.] is 1, and
+ *          |x_p| |c_p| > 0 (NaN when none counts);
+ *   q[2] = sqrt(sum r (x - c)^2) / sqrt(sum r c^2) (NaN when the denominator is 0);
+ *   q[3] = the number of pixels counted for q[1].
+ * q: device, 4 doubles.  psnr_bands: NULL or device, B doubles, receives psnr_b.  X, C and region are each
+ * read once; every sum has a fixed order (slab partials in ws, no atomics), so reruns and calls on a base
+ * misaligned by one float give the same bits.  Any P, B >= 1 with P B < 2^31; B > 512 takes a slower form of
+ * the same definition.  Never allocates, never synchronises; every refusal is decided before a launch:
+ * LRS_E_INVALID: X, C, q or ws NULL, a size <= 0.  LRS_E_UNSUPPORTED: P B >= 2^31 (the workspace size is 0
+ * there).  LRS_E_WORKSPACE: ws_bytes too small. */
+size_t lrs_cube_quality_workspace(int64_t P, int64_t B);
+int lrs_cube_quality_f32(const float *X, const float *C, const uint8_t *region, int64_t P, int64_t B, double *q,
+                         double *psnr_bands, void *ws, size_t ws_bytes, void *stream);
+/* Keep the iterate when its score is better, decided on the device (no host read).  score: device, 1 double;
+ * best: device, {score, iteration}, initialised by the caller to NaN.  Better: sign * score[0] > sign *
+ * best[0], strictly (sign +1: larger is better, -1: smaller); a NaN score never is; a NaN best[0] is beaten
+ * by any score that is not NaN.  When better, dst <- src (n floats) and best <- {score[0], iteration};
+ * otherwise nothing is written.  Two stream-ordered launches: the copy, in which every workgroup reads best
+ * for the decision, then the update of best.  LRS_E_INVALID: a NULL pointer, n <= 0, sign not +1 or -1, src
+ * overlapping dst. */
+int lrs_keep_best_f32(const double *score, int sign, int32_t iteration, const float *src, float *dst, int64_t n,
+                      double *best, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

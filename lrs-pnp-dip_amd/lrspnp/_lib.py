@@ -78,6 +78,8 @@ _TV = ("lrs_sstv_f32", "lrs_tvprox_workspace", "lrs_tvprox_f32")
 _NLMCUBE = ("lrs_nlmcube_workspace", "lrs_nlmcube_f32")
 # ... and the host-only diagnostic of the SVT calls' resolved chain
 _SVT_PLAN = ("lrs_diag_svt_plan",)
+# ... and the quality monitor
+_QUALITY = ("lrs_cube_quality_workspace", "lrs_cube_quality_f32", "lrs_keep_best_f32")
 
 
 def build(force: bool = False) -> str:
@@ -123,6 +125,9 @@ def _declare(L):
         "lrs_ssim_f32":(i32, [vp, vp, i32, i32, i32, vp, vp]),
         "lrs_psnr_workspace": (sz, [i64, i64]),
         "lrs_psnr_bands_f32": (i32, [vp, vp, i64, i64, vp, vp, sz, vp]),
+        "lrs_cube_quality_workspace": (sz, [i64, i64]),
+        "lrs_cube_quality_f32": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, sz, vp]),
+        "lrs_keep_best_f32": (i32, [vp, i32, c.c_int32, vp, vp, i64, vp, vp]),
         "lrs_svt_max_bands": (i64, []),
         "lrs_svt_workspace": (sz, [i64, i64]),
         "lrs_svt_f32": (i32, [vp, vp, f32, i64, i64, f64, vp, vp, i32, vp, sz, vp]),
@@ -198,7 +203,7 @@ def _declare(L):
         "lrs_stream_wait": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
-        if name in _PER_BAND_MASK + _FRAME + _TV + _NLMCUBE + _SVT_PLAN and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
+        if name in _PER_BAND_MASK + _FRAME + _TV + _NLMCUBE + _SVT_PLAN + _QUALITY and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
             continue   # an A/B build from before these: its other paths still time against this one
         fn = getattr(L, name)
         fn.restype = res

@@ -36,6 +36,22 @@ def mpsnr(X: torch.Tensor, clean_bhw: torch.Tensor) -> float:
     return float(psnr_bands(X, clean_bhw).mean())
 
 
+def quality(X: torch.Tensor, clean_bhw: torch.Tensor, region: torch.Tensor | None = None) -> dict:
+    """MPSNR, SAM (degrees), relative error and the per-band PSNR of the unfolded X (P x B) against clean
+    (B, H, W), over every entry or over region (P x B, nonzero = counted; 1 - M scores the hole alone): one
+    fused pass (ops.cube_quality, which states the definitions) and one read of the device at the end.
+    LrsPnP.run() is the form that scores every iteration without a host sync."""
+    from . import ops
+    B, H, W = clean_bhw.shape
+    C = ops.image_to_unfolded(clean_bhw.contiguous().float(), H, W)
+    if region is not None:
+        region = (region != 0).to(torch.uint8).contiguous()
+    out = torch.empty(4 + B, dtype=torch.float64, device=X.device)
+    ops.cube_quality(X.contiguous().float(), C, region, q=out[:4], psnr_bands=out[4:])
+    h = out.cpu().numpy()
+    return dict(mpsnr=float(h[0]), sam_deg=float(h[1]), rel_err=float(h[2]), psnr_bands=h[4:].copy())
+
+
 def mssim(img1: torch.Tensor, img2: torch.Tensor) -> float:
     """pytorch_ssim.ssim(img1, img2) for (B, H, W) (or (1, B, H, W)) float32 device images."""
     import ctypes

@@ -15,7 +15,7 @@ from ._lib import (ALPHA_FRO4, ALPHA_SOFT, ALPHA_SPEC2, PROX_NLM, PROX_NLM_MATLA
                    SVT_WARM, SVT_WIDE_MW, SVT_WIDE_TRI, TVPROX_WARM, LrsError, check, device_lib, ista_accel, lib)
 
 __all__ = ["nlm_col", "block_grid", "cover_ranges", "im2col", "ista_alpha", "ista", "svt_workspace", "svt_max_bands",
-           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "svt_plan", "tvprox_workspace", "tvprox", "nlmcube_workspace", "nlmcube", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
+           "ista_workspace", "ista_pat_plan", "ista_pat_preferred", "ista_pat_workspace", "ista_pat_prepare", "ista_pat", "dict_workspace", "dict_stats", "dict_update", "dict_normalise", "nlm_matlab_col", "svt", "svt_gram", "svt_gram_view", "svt_finish", "svt_plan", "tvprox_workspace", "tvprox", "nlmcube_workspace", "nlmcube", "cube_quality_workspace", "cube_quality", "keep_best", "admm_update", "unfolded_to_image", "image_to_unfolded", "unfolded_to_frame", "frame_to_unfolded", "masked_mse", "sstv", "mask_channels", "ALPHA_SPEC2", "ALPHA_FRO4", "ALPHA_SOFT", "PROX_NLM", "PROX_SOFT",
            "PROX_NLM_MATLAB"]
 
 
@@ -495,6 +495,66 @@ def nlmcube(X, L2, c2: float, H: int, W: int, ws, U=None, patch_size: int = 7, p
                             float(h), float(sigma), _p(U), _p(ws) if ws.numel() else None, ws.numel(), _s(stream)),
           "lrs_nlmcube_f32")
     return U
+
+
+def cube_quality_workspace(P: int, B: int, device) -> torch.Tensor:
+    """Device workspace of cube_quality() for a P x B cube (lrs_cube_quality_workspace: the slab partials)."""
+    n = int(lib().lrs_cube_quality_workspace(int(P), int(B)))
+    if n == 0:
+        raise LrsError(f"lrs_cube_quality_workspace: sizes not served (P {P}, B {B}; positive, P*B < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def cube_quality(X, C, region=None, ws=None, q=None, psnr_bands=None, stream=None):
+    """q = (MPSNR, SAM in degrees, relative error, pixels counted for SAM) of X against the clean cube C, both
+    (P, B) float32 unfolded, in one pass over both, in fp64 (lrs_cube_quality_f32, include/lrspnp.h, which
+    states the definitions).  region: None (every entry counts) or uint8 (P, B), 1 = counted.  q: a float64
+    device tensor of 4 elements; psnr_bands: None or one of B elements that receives the per-band PSNR.  No
+    host sync.  Returns q."""
+    L = device_lib()
+    _dev(X, torch.float32, "X")
+    _dev(C, torch.float32, "C")
+    if X.dim() != 2 or C.shape != X.shape:
+        raise LrsError(f"X {tuple(X.shape)} and C {tuple(C.shape)} must be the same (P, B)")
+    P, B = X.shape
+    if region is not None:
+        _dev(region, torch.uint8, "region")
+        if region.shape != X.shape:
+            raise LrsError(f"region {tuple(region.shape)} must have X's shape {tuple(X.shape)}")
+    if ws is None:
+        ws = cube_quality_workspace(P, B, X.device)
+    _dev(ws, torch.uint8, "ws")
+    if q is None:
+        q = torch.empty(4, dtype=torch.float64, device=X.device)
+    _dev(q, torch.float64, "q")
+    if q.numel() != 4:
+        raise LrsError("q must hold 4 doubles")
+    if psnr_bands is not None:
+        _dev(psnr_bands, torch.float64, "psnr_bands")
+        if psnr_bands.numel() != B:
+            raise LrsError(f"psnr_bands must hold B = {B} doubles")
+    check(L.lrs_cube_quality_f32(_p(X), _p(C), _p(region), P, B, _p(q), _p(psnr_bands), _p(ws), ws.numel(),
+                                 _s(stream)), "lrs_cube_quality_f32")
+    return q
+
+
+def keep_best(score, sign: int, iteration: int, src, dst, best, stream=None):
+    """dst <- src and best <- (score, iteration) when score (a float64 device tensor, its first element) is
+    better than best[0], decided on the device: sign +1 keeps the largest, -1 the smallest, strictly; a NaN
+    score is never kept and a NaN best[0] (how best starts) is beaten by any other (lrs_keep_best_f32).  best:
+    a float64 device tensor of 2 elements.  No host sync."""
+    L = device_lib()
+    _dev(score, torch.float64, "score")
+    _dev(best, torch.float64, "best")
+    _dev(src, torch.float32, "src")
+    _dev(dst, torch.float32, "dst")
+    if score.numel() < 1 or best.numel() != 2:
+        raise LrsError("score must hold a double and best 2 doubles")
+    if dst.numel() != src.numel():
+        raise LrsError(f"dst has {dst.numel()} elements, src {src.numel()}")
+    check(L.lrs_keep_best_f32(_p(score), int(sign), int(iteration), _p(src), _p(dst), src.numel(), _p(best),
+                              _s(stream)), "lrs_keep_best_f32")
+    return best
 
 
 def admm_update(X, L1, L2, Y, M, U, phi, bb, grid, gamma, mu1, mu2, norms=None, imout=None, stream=None):

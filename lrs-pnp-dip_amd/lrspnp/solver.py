@@ -169,6 +169,10 @@ _MODES = {"variant": tuple(_PROX), "lowrank": ("svt", "dip", "tv", "nlm"), "svt_
           "ista_accel": ("off", "fista")}
 
 
+# columns of LrsPnP.run()'s history: the three scores of ops.cube_quality, then LrsPnP.norms of the iteration
+HISTORY_COLUMNS = ("mpsnr", "sam_deg", "rel_err", "norm_dX", "norm_dL1", "norm_dL2")
+
+
 def _check_mode(name, value):
     if value not in _MODES[name]:
         raise LrsError(f"unknown {name} {value!r} ({' | '.join(_MODES[name])})")
@@ -487,6 +491,83 @@ class LrsPnP:
             late(self, main, lr)
         stream_wait(main, lr)
         self.admm(main)
+
+    def _unfolded(self, a, what):
+        """a as a contiguous float32 (P, B) device tensor: unfolded (P, B) as it is, an image (B, H, W) through
+        ops.image_to_unfolded."""
+        a = torch.as_tensor(a if isinstance(a, torch.Tensor) else np.asarray(a, np.float32), dtype=torch.float32)
+        a = a.to(self.Y.device).contiguous()
+        if a.dim() == 3 and a.shape[0] == self.B and a.shape[1] * a.shape[2] == self.P:
+            return ops.image_to_unfolded(a, a.shape[1], a.shape[2])
+        if tuple(a.shape) != (self.P, self.B):
+            raise LrsError(f"{what} must be (B, H, W) with H*W = {self.P}, B = {self.B}, or unfolded "
+                           f"({self.P}, {self.B}); got {tuple(a.shape)}")
+        return a
+
+    def run(self, n_iter, clean=None, region="all", keep_best=None):
+        """n_iter outer iterations (step()), each scored on the device against `clean`, and the best iterate
+        kept there: the loop of the reference mains (main_LRS_PnP.py:368-391: MPSNR after every iteration,
+        best_PSNR) without a host sync per iteration.
+
+        clean: the clean cube, (B, H, W) or unfolded (P, B); None records the convergence columns only.
+        region: "all", "hole" (the entries with M == 0) or an array like clean, nonzero = scored.
+        keep_best: None, or the score whose best iterate is kept: "mpsnr" (largest), "rel_err" or "sam" (smallest).
+        Per iteration, on the current stream after step(): ops.cube_quality, ops.keep_best, and the copy of the
+        three scores and of self.norms into row t of a device history.  One read at the end.  Returns the
+        history, a numpy record array of n_iter rows with the columns HISTORY_COLUMNS (norm_* are self.norms:
+        the squared norms convergence() takes the log-root of; the score columns are NaN without clean).  With
+        keep_best, self.best_X is that iterate (a device tensor), self.best_iteration its row in the history (the
+        first of equals) and self.best_score its score; None when no iteration had a score that is not NaN."""
+        n_iter = int(n_iter)
+        if n_iter < 1:
+            raise LrsError(f"run() needs n_iter >= 1, got {n_iter}")
+        if self.comm is not None:
+            raise LrsError("run() does not serve a row-slab shard (comm): its scores would be the slab's alone")
+        if keep_best is not None and keep_best not in self._KEEP:
+            raise LrsError(f"unknown keep_best {keep_best!r} ({' | '.join(self._KEEP)} | None)")
+        if clean is None and keep_best is not None:
+            raise LrsError(f"keep_best={keep_best!r} needs the clean cube: there is no score without it")
+        if isinstance(region, str) and region not in ("all", "hole"):
+            raise LrsError(f"unknown region {region!r} (all | hole | an array)")
+        dev = self.Y.device
+        # the history rows and, behind them, keep_best's {score, iteration}: one buffer, one read at the end
+        rec = torch.full((n_iter * 6 + 2,), float("nan"), dtype=torch.float64, device=dev)
+        hist = rec[: n_iter * 6].view(n_iter, 6)
+        q = best = None
+        if clean is not None:
+            C = self._unfolded(clean, "clean")
+            if isinstance(region, str):
+                reg = None if region == "all" else (self.M == 0).to(torch.uint8)
+            else:
+                reg = (self._unfolded(region, "region") != 0).to(torch.uint8)
+            ws = ops.cube_quality_workspace(self.P, self.B, dev)
+            q = torch.empty(4, dtype=torch.float64, device=dev)
+            if keep_best is not None:
+                col, sign = self._KEEP[keep_best]
+                self.best_X = torch.empty_like(self.X)
+                best = rec[n_iter * 6:]
+        self.best_iteration = self.best_score = None
+        if best is None:
+            self.best_X = None
+        for t in range(n_iter):
+            self.step()
+            if q is not None:
+                ops.cube_quality(self.X, C, reg, ws=ws, q=q)
+                if best is not None:
+                    ops.keep_best(q[col:col + 1], sign, t, self.X, self.best_X, best)
+                hist[t, :3].copy_(q[:3])
+            hist[t, 3:].copy_(self.norms)
+        h = rec.cpu().numpy()   # the one read
+        h, (score, it) = h[: n_iter * 6].reshape(n_iter, 6), h[n_iter * 6:].tolist()
+        if best is not None:
+            if score == score:
+                self.best_score, self.best_iteration = score, int(it)
+            else:
+                self.best_X = None
+        return np.rec.fromarrays(h.T, names=list(HISTORY_COLUMNS))
+
+    # keep_best -> (index in q, sign): the largest MPSNR, the smallest SAM or relative error
+    _KEEP = {"mpsnr": (0, 1), "sam": (1, -1), "rel_err": (2, -1)}
 
     def convergence(self):
         """state_convergence (main_LRS_PnP.py:23-25) of X, lambda_1, lambda_2 for the last step."""
