@@ -67,19 +67,6 @@ def dip_opts(precision: int = DIP_SPLIT_BF16, upsample_dgrad: int = 0) -> DipOpt
 
 _lib = None
 _device_checked = False
-# the entry points that take a per-band mask [C][P] (the only ones a variant build may lack)
-_PER_BAND_MASK = ("lrs_masked_mse_cmask_f32", "lrs_dipnet_train_steps_cmask")
-# ... and the ones of the reflected frame (images of a size the DIP net does not reproduce)
-_FRAME = ("lrs_masked_mse_framed_f32", "lrs_unfolded_to_frame_f32", "lrs_frame_to_unfolded_f32",
-          "lrs_dipnet_set_frame", "lrs_dipnet_get_frame")
-# ... and the TV term of the DIP output and the TV prox on the cube
-_TV = ("lrs_sstv_f32", "lrs_tvprox_workspace", "lrs_tvprox_f32")
-# ... and the non-local-means prox on the cube
-_NLMCUBE = ("lrs_nlmcube_workspace", "lrs_nlmcube_f32")
-# ... and the host-only diagnostic of the SVT calls' resolved chain
-_SVT_PLAN = ("lrs_diag_svt_plan",)
-# ... and the quality monitor
-_QUALITY = ("lrs_cube_quality_workspace", "lrs_cube_quality_f32", "lrs_keep_best_f32")
 
 
 def build(force: bool = False) -> str:
@@ -202,9 +189,13 @@ def _declare(L):
         "lrs_dipnet_last_loss": (i32, [vp, c.POINTER(f64), vp]),
         "lrs_stream_wait": (i32, [vp, vp]),
     }
+    # The product library must export every row.  A variant build named by LRSPNP_LIB (A/B timing) may predate
+    # some: a row it lacks is skipped, so its other paths still time against this one, and a call of a
+    # skipped entry point then fails at that call (ctypes' AttributeError), not at load.
+    variant = bool(os.environ.get("LRSPNP_LIB"))
     for name, (res, args) in sig.items():
-        if name in _PER_BAND_MASK + _FRAME + _TV + _NLMCUBE + _SVT_PLAN + _QUALITY and "LRSPNP_LIB" in os.environ and not hasattr(L, name):
-            continue   # an A/B build from before these: its other paths still time against this one
+        if variant and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -243,3 +234,55 @@ def device_lib():
 def check(rc: int, what: str) -> None:
     if rc != LRS_OK:
         raise LrsError(f"{what} failed: {LRS_E.get(rc, f'hipError {rc}')}")
+
+
+# ---- what every wrapper (ops, dip, metrics) passes to the library ---------------------------------------
+def ptr(t):
+    """A tensor's device pointer (None stays NULL)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def sptr(stream=None):
+    """A torch stream's hipStream_t (None: the current stream)."""
+    if stream is None:
+        import torch
+
+        stream = torch.cuda.current_stream()
+    return ctypes.c_void_p(stream.cuda_stream)
+
+
+def dev(t, dtype, name):
+    """t, after checking that it is a contiguous device tensor of dtype."""
+    import torch
+
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise LrsError(f"{name} must be a CUDA(ROCm) tensor")
+    if t.dtype != dtype:
+        raise LrsError(f"{name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise LrsError(f"{name} must be contiguous")
+    return t
+
+
+def outs(fn, what: str, *args, n: int = 3, ctype=ctypes.c_int) -> tuple:
+    """fn(*args, &o_0, ..., &o_{n-1}), checked: the values of its n trailing out-parameters of ctype."""
+    o = [ctype() for _ in range(n)]
+    check(fn(*args, *[ctypes.byref(x) for x in o]), what)
+    return tuple(x.value for x in o)
+
+
+def mask_channels(mask, C: int, P: int, hw=("H", "W")) -> int:
+    """The mode of a DIP loss mask for a C x P output: 1 for a pixel mask (P elements, applied to every
+    channel), C for a per-element mask (C*P elements, the layout of the output: a mask that differs
+    between bands); None (no mask) counts as 1.  Anything else is refused; hw: the image's (H, W) where the
+    caller knows it, for that message."""
+    if mask is None:
+        return 1
+    n = mask.numel()
+    if n == P:
+        return 1
+    if n == C * P:
+        return C
+    H, W = hw
+    raise LrsError(f"mask has {n} elements ({tuple(mask.shape)}): expected a pixel mask ({P},) / ({H}, {W}) or a "
+                   f"per-band mask ({C}, {H}, {W})")

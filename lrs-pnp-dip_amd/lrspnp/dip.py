@@ -23,6 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._lib import check, outs, ptr, sptr
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_LRELU, ACT_SIGMOID, ACT_RELU = 0, 1, 2, 3   # ReLU: the DECODE stage only
@@ -168,15 +169,6 @@ UNET_REF_NAMES = (
 )
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise _lib.LrsError(f"{what} failed: {_lib.LRS_E.get(rc, rc)}")
-
-
 # Orders the DIP stream against the caller's with a device-scope event (lrs_stream_wait) instead of
 # torch's wait_stream (an event with the default system-scope release); False: torch's (A/B only).
 DEVICE_SCOPE_WAITS = True
@@ -187,8 +179,7 @@ def stream_wait(waiter, signaler):
     if not DEVICE_SCOPE_WAITS:
         waiter.wait_stream(signaler)
         return
-    _check(_lib.device_lib().lrs_stream_wait(ctypes.c_void_p(waiter.cuda_stream), ctypes.c_void_p(signaler.cuda_stream)),
-           "lrs_stream_wait")
+    check(_lib.device_lib().lrs_stream_wait(sptr(waiter), sptr(signaler)), "lrs_stream_wait")
 
 
 class DipNet:
@@ -208,8 +199,8 @@ class DipNet:
         arr = (DipNode * len(nodes))(*nodes)
         h = ctypes.c_void_p()
         self.opts = _lib.dip_opts(precision, upsample_dgrad)
-        _check(self.L.lrs_dipnet_create(arr, len(nodes), C, H, W, ctypes.byref(self.opts), ctypes.byref(h)),
-               "lrs_dipnet_create")
+        check(self.L.lrs_dipnet_create(arr, len(nodes), C, H, W, ctypes.byref(self.opts), ctypes.byref(h)),
+              "lrs_dipnet_create")
         self.h = h
         self.H, self.W = H, W
         self.n_params = int(self.L.lrs_dipnet_num_params(h))
@@ -224,23 +215,13 @@ class DipNet:
         self.exp_avg_sq = torch.zeros(self.n_params, **f32)
         self.bnstats = bnstats if bnstats is not None else torch.zeros(max(nbs, 1), **f32)
         self.ws = torch.zeros(ws, dtype=torch.uint8, device=device)
-        _check(self.L.lrs_dipnet_bind(h, _ptr(self.params), _ptr(self.grads), _ptr(self.exp_avg),
-                                      _ptr(self.exp_avg_sq), _ptr(self.bnstats), _ptr(self.ws), ws),
-               "lrs_dipnet_bind")
-        c, ho, wo = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        self.L.lrs_dipnet_out_shape(h, ctypes.byref(c), ctypes.byref(ho), ctypes.byref(wo))
-        self.out_shape = (c.value, ho.value, wo.value)
+        check(self.L.lrs_dipnet_bind(h, ptr(self.params), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                                     ptr(self.bnstats), ptr(self.ws), ws), "lrs_dipnet_bind")
+        self.out_shape = outs(self.L.lrs_dipnet_out_shape, "lrs_dipnet_out_shape", h)
         self.in_shape = (C, H, W)
-        self.shapes = []
-        for i in range(len(nodes)):
-            cc, hh, ww = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-            self.L.lrs_dipnet_node_shape(h, i, ctypes.byref(cc), ctypes.byref(hh), ctypes.byref(ww))
-            self.shapes.append((cc.value, hh.value, ww.value))
-        self.offsets = []
-        for i in range(len(nodes)):
-            o = [ctypes.c_int64() for _ in range(4)]
-            self.L.lrs_dipnet_param_offsets(h, i, *[ctypes.byref(x) for x in o])
-            self.offsets.append(tuple(x.value for x in o))
+        self.shapes = [outs(self.L.lrs_dipnet_node_shape, "lrs_dipnet_node_shape", h, i) for i in range(len(nodes))]
+        self.offsets = [outs(self.L.lrs_dipnet_param_offsets, "lrs_dipnet_param_offsets", h, i, n=4,
+                             ctype=ctypes.c_int64) for i in range(len(nodes))]
         self.stream = torch.cuda.Stream(device=device, priority=int(stream_priority))
         self._es = None
         self.frame = (0, 0) + self.out_shape[1:]    # (top, left, H, W): the whole output, no frame
@@ -265,8 +246,8 @@ class DipNet:
     # ---- parameters ---------------------------------------------------------------------------
     def init_params(self, seed: int):
         """Fresh parameters and optimizer state, enqueued on the engine stream."""
-        _check(self.L.lrs_dipnet_init_params(self.h, ctypes.c_uint64(seed & (2**64 - 1)),
-                                             ctypes.c_void_p(self.stream.cuda_stream)), "init_params")
+        check(self.L.lrs_dipnet_init_params(self.h, ctypes.c_uint64(seed & (2**64 - 1)), sptr(self.stream)),
+              "init_params")
 
     def param_views(self, i: int, flat=None):
         """(weight [cout,cin,k,k] | None, bias | None, gamma | None, beta | None) of node i, as views
@@ -301,8 +282,7 @@ class DipNet:
 
     def reset_optimizer(self):
         """Zero the Adam moments and the step count (a fresh torch.optim.Adam)."""
-        _check(self.L.lrs_dipnet_reset_optimizer(self.h, ctypes.c_void_p(self.stream.cuda_stream)),
-               "lrs_dipnet_reset_optimizer")
+        check(self.L.lrs_dipnet_reset_optimizer(self.h, sptr(self.stream)), "lrs_dipnet_reset_optimizer")
         self.stream.synchronize()
 
     # ---- compute ------------------------------------------------------------------------------
@@ -312,8 +292,7 @@ class DipNet:
         x = x.contiguous()
         assert tuple(x.shape[-3:]) == self.in_shape and x.dtype == torch.float32 and x.is_cuda
         self.stream.wait_stream(torch.cuda.current_stream())
-        _check(self.L.lrs_dipnet_forward(self.h, _ptr(x), ctypes.c_void_p(self.stream.cuda_stream)),
-               "lrs_dipnet_forward")
+        check(self.L.lrs_dipnet_forward(self.h, ptr(x), sptr(self.stream)), "lrs_dipnet_forward")
         torch.cuda.current_stream().wait_stream(self.stream)
         return self.output()
 
@@ -323,12 +302,11 @@ class DipNet:
         x, gout = x.contiguous(), gout.contiguous()
         assert tuple(gout.shape[-3:]) == self.out_shape and gout.dtype == torch.float32 and gout.is_cuda
         self.stream.wait_stream(torch.cuda.current_stream())
-        _check(self.L.lrs_dipnet_backward(self.h, _ptr(x), _ptr(gout), ctypes.c_void_p(self.stream.cuda_stream)),
-               "lrs_dipnet_backward")
+        check(self.L.lrs_dipnet_backward(self.h, ptr(x), ptr(gout), sptr(self.stream)), "lrs_dipnet_backward")
         torch.cuda.current_stream().wait_stream(self.stream)
 
     def set_ln_lambda(self, ln_lambda: float):
-        _check(self.L.lrs_dipnet_set_ln_lambda(self.h, ctypes.c_float(ln_lambda)), "lrs_dipnet_set_ln_lambda")
+        check(self.L.lrs_dipnet_set_ln_lambda(self.h, ctypes.c_float(ln_lambda)), "lrs_dipnet_set_ln_lambda")
 
     def output(self):
         import torch
@@ -350,13 +328,13 @@ class DipNet:
         mc = self.mask_channels(mask)
         stream_wait(self.stream, torch.cuda.current_stream())
         tail = (ctypes.c_float(lr), ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(eps),
-                _ptr(es.state) if es else None, _ptr(es.ring) if es else None, int(nsteps), 1 if use_graph else 0,
-                ctypes.c_void_p(self.stream.cuda_stream))
+                ptr(es.state) if es else None, ptr(es.ring) if es else None, int(nsteps), 1 if use_graph else 0,
+                sptr(self.stream))
         if mc == 1:
-            rc = self.L.lrs_dipnet_train_steps(self.h, _ptr(x), _ptr(target), _ptr(mask), *tail)
+            rc = self.L.lrs_dipnet_train_steps(self.h, ptr(x), ptr(target), ptr(mask), *tail)
         else:
-            rc = self.L.lrs_dipnet_train_steps_cmask(self.h, _ptr(x), _ptr(target), _ptr(mask), mc, *tail)
-        _check(rc, "lrs_dipnet_train_steps")
+            rc = self.L.lrs_dipnet_train_steps_cmask(self.h, ptr(x), ptr(target), ptr(mask), mc, *tail)
+        check(rc, "lrs_dipnet_train_steps")
         stream_wait(torch.cuda.current_stream(), self.stream)
 
     def mask_channels(self, mask) -> int:
@@ -364,17 +342,10 @@ class DipNet:
         net's output; LrsError for any other size, or a mask the engine cannot read in place."""
         import torch
         C, H, W = self.out_shape
-        if mask is None:
-            return 1
-        n = mask.numel()
-        if n not in (H * W, C * H * W):
-            raise _lib.LrsError(f"mask has {n} elements ({tuple(mask.shape)}): expected a pixel mask ({H * W},) / "
-                                f"({H}, {W}) or a per-band mask ({C}, {H}, {W})")
-        if n == H * W:
-            return 1
-        if mask.dtype != torch.float32 or not mask.is_cuda or not mask.is_contiguous():
+        mc = _lib.mask_channels(mask, C, H * W, (H, W))
+        if mc != 1 and (mask.dtype != torch.float32 or not mask.is_cuda or not mask.is_contiguous()):
             raise _lib.LrsError("a per-band mask must be a contiguous float32 tensor on the device")
-        return C
+        return mc
 
     def node_buffer(self, node: int, which: int = 0):
         """A copy of node `node`'s workspace buffer (0 output, 1 pre-BN z, 2 dL/dz, 3 dL/d(output);
@@ -383,19 +354,17 @@ class DipNet:
         ptr = int(self.L.lrs_dipnet_node_buffer(self.h, int(node), int(which)))
         if not ptr:
             return None
-        c, h, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        self.L.lrs_dipnet_node_shape(self.h, int(node), ctypes.byref(c), ctypes.byref(h), ctypes.byref(w))
-        n = c.value * h.value * w.value
+        c, h, w = outs(self.L.lrs_dipnet_node_shape, "lrs_dipnet_node_shape", self.h, int(node))
+        n = c * h * w
         base = self.ws.data_ptr()
         off = (ptr - base) // 4
         assert 0 <= off and (ptr - base) % 4 == 0 and off + n <= self.ws.numel() // 4
         torch.cuda.synchronize()
-        return self.ws.view(torch.float32)[off:off + n].clone().view(c.value, h.value, w.value)
+        return self.ws.view(torch.float32)[off:off + n].clone().view(c, h, w)
 
     def last_loss(self) -> float:
         v = ctypes.c_double()
-        _check(self.L.lrs_dipnet_last_loss(self.h, ctypes.byref(v), ctypes.c_void_p(self.stream.cuda_stream)),
-               "lrs_dipnet_last_loss")
+        check(self.L.lrs_dipnet_last_loss(self.h, ctypes.byref(v), sptr(self.stream)), "lrs_dipnet_last_loss")
         return v.value
 
 
@@ -411,7 +380,7 @@ class EarlyStopper:
         # the ring [size][N] floats, then the sliding window sums (lrs_es_ring_bytes)
         self.ring = torch.zeros((L.lrs_es_ring_bytes(size, n_elems) + 3) // 4, dtype=torch.float32, device=device)
         self._host = None
-        _check(L.lrs_es_init(_ptr(self.state), size, patience, None), "lrs_es_init")
+        check(L.lrs_es_init(ptr(self.state), size, patience, None), "lrs_es_init")
 
     def read(self, stream=None) -> EsState:
         """Copy the state to the host after the work queued on `stream` (default: current)."""
@@ -533,15 +502,11 @@ class DipProx:
         else:
             key = (mask.data_ptr(), tuple(mask.shape), mask._version)
         C, P, Pf = self.net.out_shape[0], self.H * self.W, self.Hf * self.Wf
-        n = mask.numel()
-        if n not in (P, C * P):
-            if n in (Pf, C * Pf):
-                return mask
-            raise _lib.LrsError(f"mask has {n} elements ({tuple(mask.shape)}): expected a pixel mask ({P},) / "
-                                f"({self.H}, {self.W}) or a per-band mask ({C}, {self.H}, {self.W})")
+        if mask.numel() not in (P, C * P) and mask.numel() in (Pf, C * Pf):
+            return mask
+        ch = _lib.mask_channels(mask, C, P, (self.H, self.W))   # any other size is refused here
         if self._mask_framed is not None and key == self._mask_key:
             return self._mask_framed
-        ch = n // P
         m = torch.zeros((ch, self.Hf, self.Wf), dtype=torch.float32, device=mask.device)
         self.crop(m).copy_(mask.reshape(ch, self.H, self.W))
         self._mask_key, self._mask_framed = key, (m.reshape(-1) if ch == 1 else m)
@@ -586,8 +551,7 @@ class DipProx:
                 return self.crop(self.last_framed)
             return net.output()                    # the last step's forward output (`out`)
         L = _lib.device_lib()
-        _check(L.lrs_es_init(_ptr(self.es.state), cfg.es_size, cfg.patience, ctypes.c_void_p(net.stream.cuda_stream)),
-               "lrs_es_init")
+        check(L.lrs_es_init(ptr(self.es.state), cfg.es_size, cfg.patience, sptr(net.stream)), "lrs_es_init")
         done = 0
         st = None
         while done < n_iter:
@@ -659,18 +623,14 @@ def sigma_max(weights, ln_lambda: float = 1.0):
     sc = torch.empty_like(sig)
     nb = int(L.lrs_sigma_max_workspace(n))
     ws = torch.empty(nb, dtype=torch.uint8, device=mats[0].device)
-    s = torch.cuda.current_stream().cuda_stream
-    _check(L.lrs_sigma_max_f32(W, None, rows, cols, n, ctypes.c_float(ln_lambda), _ptr(sig), _ptr(sc),
-                               _ptr(ws), nb, ctypes.c_void_p(s)), "lrs_sigma_max_f32")
+    check(L.lrs_sigma_max_f32(W, None, rows, cols, n, ctypes.c_float(ln_lambda), ptr(sig), ptr(sc), ptr(ws), nb,
+                              sptr()), "lrs_sigma_max_f32")
     return sig, sc
 
 
 def out_size(H, W, k, stride, pad, up):
     """Output size of one unit; up: 0 none, non-zero x2 (nearest, or UP_BILINEAR of a DECODE stage)."""
-    ho, wo = ctypes.c_int(), ctypes.c_int()
-    _check(_lib.lib().lrs_conv2d_out_size(H, W, k, stride, pad, up, ctypes.byref(ho), ctypes.byref(wo)),
-           "lrs_conv2d_out_size")
-    return ho.value, wo.value
+    return outs(_lib.lib().lrs_conv2d_out_size, "lrs_conv2d_out_size", H, W, k, stride, pad, up, n=2)
 
 
 def unet_size_ok(H: int, W: int) -> bool:
@@ -692,9 +652,7 @@ def net_out_hw(nodes, H: int, W: int):
     if L.lrs_dipnet_create(arr, len(nodes), 1, int(H), int(W), ctypes.byref(opts), ctypes.byref(h)) != 0:
         return None
     try:
-        c, ho, wo = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        L.lrs_dipnet_out_shape(h, ctypes.byref(c), ctypes.byref(ho), ctypes.byref(wo))
-        return ho.value, wo.value
+        return outs(L.lrs_dipnet_out_shape, "lrs_dipnet_out_shape", h)[1:]
     finally:
         L.lrs_dipnet_destroy(h)
 

@@ -15,10 +15,8 @@ def fold(X: torch.Tensor, H: int, W: int) -> torch.Tensor:
 
 def psnr_bands(X: torch.Tensor, clean_bhw: torch.Tensor) -> torch.Tensor:
     """Per-band PSNR (device float64 [B]) of the unfolded X (P x B) against clean (B, H, W)."""
-    import ctypes
-
     from . import ops
-    from ._lib import check, device_lib
+    from ._lib import check, device_lib, ptr, sptr
     B, H, W = clean_bhw.shape
     C = ops.image_to_unfolded(clean_bhw.contiguous().float(), H, W)
     Xc = X.contiguous().float()
@@ -26,9 +24,7 @@ def psnr_bands(X: torch.Tensor, clean_bhw: torch.Tensor) -> torch.Tensor:
     P = H * W
     ws = torch.empty(int(L.lrs_psnr_workspace(P, B)), dtype=torch.uint8, device=X.device)
     out = torch.empty(B, dtype=torch.float64, device=X.device)
-    vp = ctypes.c_void_p
-    check(L.lrs_psnr_bands_f32(vp(Xc.data_ptr()), vp(C.data_ptr()), P, B, vp(out.data_ptr()), vp(ws.data_ptr()),
-                               ws.numel(), vp(torch.cuda.current_stream().cuda_stream)), "lrs_psnr_bands_f32")
+    check(L.lrs_psnr_bands_f32(ptr(Xc), ptr(C), P, B, ptr(out), ptr(ws), ws.numel(), sptr()), "lrs_psnr_bands_f32")
     return out
 
 
@@ -54,14 +50,10 @@ def quality(X: torch.Tensor, clean_bhw: torch.Tensor, region: torch.Tensor | Non
 
 def mssim(img1: torch.Tensor, img2: torch.Tensor) -> float:
     """pytorch_ssim.ssim(img1, img2) for (B, H, W) (or (1, B, H, W)) float32 device images."""
-    import ctypes
-
-    from ._lib import check, device_lib
+    from ._lib import check, device_lib, ptr, sptr
     a = img1.reshape(-1, *img1.shape[-2:]).contiguous().float()
     b = img2.reshape(-1, *img2.shape[-2:]).contiguous().float()
     C, H, W = a.shape
     acc = torch.zeros(1, dtype=torch.float64, device=a.device)
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    check(device_lib().lrs_ssim_f32(ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), C, H, W,
-                                    ctypes.c_void_p(acc.data_ptr()), s), "lrs_ssim_f32")
+    check(device_lib().lrs_ssim_f32(ptr(a), ptr(b), C, H, W, ptr(acc), sptr()), "lrs_ssim_f32")
     return float(acc) / (C * H * W)

@@ -26,6 +26,86 @@ def test_library_exports_header_symbols():
     assert _lib.lib().lrs_version().startswith(b"lrspnp-hip")
 
 
+def header_prototypes():
+    """{name: (return type, [parameter types])} of every lrs_* prototype of include/lrspnp.h, as C text."""
+    src = open(os.path.join(REPO, "include", "lrspnp.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)                       # comments
+    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)                        # preprocessor lines
+    src = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", " ", src, flags=re.S)
+    protos = {}
+    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(lrs_\w+)\s*\(([^()]*)\)\s*;", src):
+        args = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
+        assert name not in protos, name
+        protos[name] = (ret.strip(), args)
+    return protos
+
+
+C_CLASS = {"int": "int", "int32_t": "int", "int64_t": "int64", "float": "float", "double": "double",
+           "size_t": "size", "uint64_t": "size", "void": "void"}
+CTYPES_CLASS = {ctypes.c_int: "int", ctypes.c_int32: "int", ctypes.c_int64: "int64", ctypes.c_float: "float",
+                ctypes.c_double: "double", ctypes.c_size_t: "size", ctypes.c_uint64: "size", None: "void",
+                ctypes.c_void_p: "pointer", ctypes.c_char_p: "pointer"}
+# Returns the header declares as `const float *` and the table reads as size_t on purpose:
+POINTER_AS_SIZE = {
+    "lrs_dipnet_output",       # DipNet.output() subtracts the workspace's base address from it to find its view
+    "lrs_dipnet_grads",        # the same kind of address, for the same arithmetic (an integer, never dereferenced)
+    "lrs_dipnet_node_buffer",  # DipNet.node_buffer(): an integer offset into the workspace, and 0 (not None) for NULL
+}
+
+
+def c_class(decl: str, is_param: bool) -> str:
+    if "*" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    if is_param and len(words) > 1:
+        words = words[:-1]                     # the parameter's name
+    assert len(words) == 1 and words[0] in C_CLASS, decl
+    return C_CLASS[words[0]]
+
+
+def ctypes_class(t) -> str:
+    if t in CTYPES_CLASS:
+        return CTYPES_CLASS[t]
+    assert isinstance(t, type) and issubclass(t, ctypes._Pointer), t
+    return "pointer"
+
+
+def test_signature_table_matches_header():
+    """A wrong ctypes width is silent at run time: a row of _lib._declare's table with c_int where the header says
+    int64_t, or c_float where it says double, hands a kernel garbage and raises nothing.  So every row's restype and
+    argtypes are compared, class by class (pointer, int, int64, float, double, size_t / uint64_t, void), with the
+    prototype of include/lrspnp.h; every prototype has a row; and the only rows without one are the diagnostics
+    entry points csrc/svt.hip and csrc/dipnet.hip define outside the header."""
+    class Recorder:                            # stands in for the loaded library: keeps what _declare sets
+        def __init__(self):
+            self.rows = {}
+
+        def __getattr__(self, name):
+            if not name.startswith("lrs_"):
+                raise AttributeError(name)
+            return self.rows.setdefault(name, type("Row", (), {})())
+
+    rows = _lib._declare(Recorder()).rows
+    protos = header_prototypes()
+    assert len(protos) >= 89 and set(protos) == set(declared_symbols())
+    assert not set(protos) - set(rows), sorted(set(protos) - set(rows))
+    diag = set()
+    for f in ("svt.hip", "dipnet.hip"):
+        with open(os.path.join(REPO, "lrs-pnp-dip_amd", "csrc", f)) as fh:
+            diag |= set(re.findall(r'extern "C"[^;{(]*?\b(lrs_diag_\w+)\s*\(', fh.read()))
+    assert len(diag) == 4 and set(rows) - set(protos) == diag, (sorted(set(rows) - set(protos)), sorted(diag))
+    wrong = []
+    for name, (ret, args) in sorted(protos.items()):
+        want = [c_class(ret, False)] + [c_class(a, True) for a in args]
+        if name in POINTER_AS_SIZE:
+            assert want[0] == "pointer", name
+            want[0] = "size"
+        got = [ctypes_class(rows[name].restype)] + [ctypes_class(t) for t in rows[name].argtypes]
+        if got != want:
+            wrong.append((name, want, got))
+    assert not wrong, wrong
+
+
 def test_no_process_wide_mode():
     """reentrant, no global mutable state.  Every mode is a per-call option
     (lrs_ista_opts, lrs_dip_opts) or fixed per handle; the only setter takes a lrs_dipnet; the
