@@ -269,7 +269,13 @@ typedef struct {
  *     workgroups; fixed-order sums, so reruns are bit-identical); every later phase is the same.
  *     _gram treats it as LRS_SVT_WIDE_TRI alone.  Diagnostic state word 7 is 1 after such a solve
  *     and 0 after a solve of the one-workgroup reduction; the path is still 4 or 5.  The workspace
- *     is the same size: the reduction's scratch aliases regions that are dead while it runs. */
+ *     is the same size: the reduction's scratch aliases regions that are dead while it runs.
+ * What ws holds before a call: a cold call of a wide cube (256 < B <= 512; the flag word 0,
+ * LRS_SVT_WIDE_TRI, or LRS_SVT_WIDE_TRI | LRS_SVT_WIDE_MW) ignores the workspace's contents.  It
+ * clears the state words itself and reads nothing past them that it has not written in the same
+ * call, so it needs no zeroed workspace and gives the same bits after any earlier call of any chain
+ * on that ws.  Only a call with LRS_SVT_WARM reads what the call before it left (the state words
+ * and the eigenvectors), and needs the first 256 bytes of a new ws to be zero. */
 #define LRS_SVT_WARM 1
 #define LRS_SVT_JACOBI 2
 #define LRS_SVT_MULTI_WG 4

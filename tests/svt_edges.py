@@ -1,4 +1,5 @@
-"""Hard spectra and edge shapes for the SVT prox of at most 256 bands, with their fp64 reference.
+"""Hard spectra and edge shapes for the SVT prox, with their fp64 reference: a matrix for at most 256 bands
+and a wide one for 257 to 512.
 
 The chain (csrc/svt.hip's header) computes U = Z (I - E) with E = V diag(min(tau / s, 1)) V^T from an fp64
 eigendecomposition of the Gram and rounds E to float32 before the product.  Where the result is small beside
@@ -8,7 +9,10 @@ restatement of the design's float32 stage (no port of any kernel): the bounds of
 are checked on it and on float32 LAPACK (oracle.svt), without the code under test.
 
 The case matrix: cases(P, B) for the shapes of SPECTRA_SHAPES (seven spectra each) and of EDGE_SHAPES (one
-dense Gaussian each), built once per shape with their references, arrays read-only.  Needs numpy alone.
+dense Gaussian each), built once per shape with their references, arrays read-only.  The wide matrix
+(WIDE_SPECTRA_SHAPES, WIDE_EDGE_SHAPES, WIDE_CASE_IDS: the chains of csrc/svt_wide.h, svt_wide_eig.h and
+svt_wide_mw.h) is built by the same functions with the same spectra and bounds, whose derivations do not
+depend on the band count.  Needs numpy alone.
 """
 import functools
 
@@ -29,6 +33,27 @@ EDGE_SHAPES = (
     (63, 16), (64, 16), (65, 16), (257, 33),        # the apply's 64-row edge; empty Gram slabs (P < 256, 257)
 )
 SCALES = (("scaled1e-4", 1e-4), ("scaled1e3", 1e3))
+
+# 256 < B <= 512.  k_gram_wide works on panels of 64 columns (4 tiles of 16, nt = ceil(B / 16) tiles kept),
+# k_svt_apply_f<2, 8, 0> on panels of 128 columns in ceil(B / 8) pairs of k-steps; Bp is B rounded up to even.
+#   257  the first wide count, odd (Bp = 258): the fifth Gram panel and the third apply panel hold one
+#        column, nt = 17, B mod 8 = 1
+#   258  the same Bp without the pad
+#   320  five Gram panels exactly, B mod 8 = 0, two and a half apply panels
+#   321  one column past 320
+#   385  one column past three apply panels and six Gram panels, odd
+#   448  the Specim FX10 count: seven Gram panels, three and a half apply panels
+#   511  odd with Bp at the cap: the pad is row and column 511
+#   512  the cap
+WIDE_BANDS = (257, 258, 320, 321, 385, 448, 511, 512)
+WIDE_SPECTRA_SHAPES = tuple((3 * B + 5, B) for B in WIDE_BANDS)
+WIDE_EDGE_SHAPES = (
+    (1, 257), (3, 300),                             # one slab of 4 staged rows; rank 1 and rank 3
+    (127, 258), (128, 258), (129, 258),             # the apply's 128-row workgroup edge; P < B: rank-deficient Gram
+    (100, 512), (200, 511),                         # P < B at the cap
+    (1024, 257), (1025, 257),                       # 32 rows per slab (one LDS chunk exactly); 36 (a second chunk of 4)
+    (1030, 321),                                    # a last slab of 22 rows, staged as 24
+)
 
 
 def u_bound(B):
@@ -118,10 +143,10 @@ def edge_case(P, B):
 @functools.lru_cache(maxsize=None)
 def cases(P, B):
     """The cases of a shape as a tuple of (name, Z, tau, U*, s*), built once, the arrays read-only."""
-    if (P, B) in SPECTRA_SHAPES:
+    if (P, B) in SPECTRA_SHAPES + WIDE_SPECTRA_SHAPES:
         todo = [(name, spectrum_case(P, B, s, _seed(name, B)), tau) for name, s, tau in spectra(B)]
     else:
-        assert (P, B) in EDGE_SHAPES, (P, B)
+        assert (P, B) in EDGE_SHAPES + WIDE_EDGE_SHAPES, (P, B)
         todo = [("dense",) + edge_case(P, B)]
     out = []
     for name, Z, tau in todo:
@@ -144,3 +169,5 @@ def case_matrix():
 # ids of the matrix for pytest.mark.parametrize, without building anything
 CASE_IDS = ([(P, B, name) for P, B in SPECTRA_SHAPES for name, _, _ in spectra(B)]
             + [(P, B, "dense") for P, B in EDGE_SHAPES])
+WIDE_CASE_IDS = ([(P, B, name) for P, B in WIDE_SPECTRA_SHAPES for name, _, _ in spectra(B)]
+                 + [(P, B, "dense") for P, B in WIDE_EDGE_SHAPES])
